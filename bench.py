@@ -12,8 +12,30 @@ Other workloads of BASELINE.json (parity-tested configurations; their lines go t
 
 One step = teacher fwd + ERS + NMS + student fwd + the five loss groups + student backward + gradient mean over
 ranks (RCCL) + SGD update, on one synthetic batch already resident in HBM (BASELINE.json configs[1]: bs=4 per GPU,
-fp32, procedural weights).  Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, measured with HIP events
-on the launch stream over the timed region) and, at N=1, `cpu_baseline` (the oracle restatement timed on the host).
+fp32, procedural weights).  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline (`value`, `ms_per_step`) and nothing it
+would need further runs for.  `--full` adds the legs that take runs of their own: `roofline` / `kernels` (per-kernel HIP
+events over extra serialized steps), `strict_fp32` (the `--compute f32` sibling) and, at N=1, `cpu_baseline` (the oracle
+restatement timed on the host); `--no-kernel-timing` / `--no-strict-fp32` / `--no-cpu-baseline` drop single legs of it.
+
+`--dump-outputs DIR` writes what the timed path (`ERDTrainer.train_step`) computes in the last timed step -- same batch,
+same iteration and learning rate, with the batched BN fold / prepared weights, the momentum branch of the update and the
+teacher look-ahead all in steady state -- replayed after the timed region on a trainer built afresh from the seeded weights:
+the fresh trainer is set to iteration j-1 and steps once on batch j-1 (announcing batch j), then the dumped step runs on
+batch j (j = warmup + steps - 1).  Rank 0 writes; every rank takes the steps.
+  <loss key>.npy       float64, the values of the dict `ERDTrainer.train_step` returns (loss, loss_cls, ...)
+  grad_norms.npy       float64 [P], L2 norm of each trainable parameter's gradient (trainer layout order)
+  param_norms.npy      float64 [P], L2 norm of each trainable parameter after the step's SGD update
+  grad_sample.npy      float32, a fixed seeded sample of the concatenated gradients (all of them when small enough)
+  param_sample.npy     float32, the updated parameters at the same positions
+  update_sample.npy    float32, the step's SGD update at those positions (parameter after minus before, exact)
+  sample_index.npy     float64, those positions in the concatenation
+What it does not cover: the weights the timed trainer itself reached.  Its trajectory is not reproducible -- the gradients of
+the 1-d parameters (BN / GN affine, biases, head scales) are float-atomic column sums whose last bits vary from run to run,
+every update carries that into the weights, and two runs of the same command end their timed steps at different losses
+(profiles/dump_repro.txt).  The replayed step starts from weights and optimizer state that are the same on every run, so
+its outputs differ between runs by that rounding alone (measured in the same file; tools/compare_dumps.py compares two dumps).
 """
 from __future__ import annotations
 
@@ -253,6 +275,40 @@ def pmc_mfma_busy(symbol_prefix: str, compute: str = "f32"):
     return (round(sum(a * b for a, b in rows) / n, 4), "profiles/" + os.path.basename(f)) if n else (None, None)
 
 
+DUMP_SAMPLE = 1 << 21      # elements of the gradient / parameter / update samples of --dump-outputs (8 + 8 + 8 + 16 MB)
+
+
+def dump_index(trainer) -> np.ndarray:
+    """positions of the --dump-outputs samples in the concatenation of the trainable parameters (fixed seed)"""
+    total = sum(p.numel() for p in trainer.flat.params)
+    return np.arange(total) if total <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(total, DUMP_SAMPLE, replace=False))
+
+
+def param_sample(trainer, idx: np.ndarray) -> torch.Tensor:
+    sel = torch.from_numpy(idx).to(trainer.flat.params[0].device)
+    return torch.cat([p.detach().reshape(-1) for p in trainer.flat.params]).index_select(0, sel)
+
+
+def dump_outputs(out_dir: str, log, trainer, idx: np.ndarray, before: torch.Tensor) -> None:
+    """--dump-outputs: one step's results as DIR/<name>.npy (float32 / float64, 42 MB at most; see the module docstring).
+    `before`: param_sample(trainer, idx) taken right before the step"""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for k, v in log.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.asarray(float(v.detach() if torch.is_tensor(v) else v), dtype=np.float64))
+    params = trainer.flat.params
+    np.save(os.path.join(out_dir, "grad_norms.npy"),
+            torch.stack([p.grad.detach().double().norm() for p in params]).cpu().numpy())
+    np.save(os.path.join(out_dir, "param_norms.npy"), torch.stack([p.detach().double().norm() for p in params]).cpu().numpy())
+    sel = torch.from_numpy(idx).to(params[0].device)
+    np.save(os.path.join(out_dir, "grad_sample.npy"),
+            torch.cat([p.grad.detach().reshape(-1) for p in params]).index_select(0, sel).float().cpu().numpy())
+    after = param_sample(trainer, idx)
+    np.save(os.path.join(out_dir, "param_sample.npy"), after.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "update_sample.npy"), (after - before).float().cpu().numpy())    # (|update| << |w|: exact in fp32)
+    np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+
+
 def self_launch(args, argv) -> int:
     """`python bench.py --gpus N` without a torchrun environment: start the N ranks ourselves, as the reference's launcher
     does (tools/dist_train.sh:11-19 -> torch.distributed.launch; configs/_base_/default_runtime.py:14 backend 'nccl').
@@ -303,10 +359,16 @@ def main():
     ap.add_argument("--mixed-res", action="store_true",
                     help="BASELINE configs[4]: every batch draws its (h, w) from the five landscape shapes of SURVEY 8(d); the frozen "
                          "teacher is replayed from one hipGraph per padded shape (implies --teacher-graph)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: the per-kernel roofline pass, the strict-fp32 leg and (N = 1) the "
+                         "CPU baseline.  Off: the run does only what `value` / `ms_per_step` need")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, one more step on the last timed batch from the built weights: its losses and a fixed "
+                         "sample of its gradients / updated parameters go to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the roofline pass")
     ap.add_argument("--no-strict-fp32", action="store_true",
-                    help="skip the short `--compute f32` leg whose rate the f32x3 line carries as `strict_fp32`")
+                    help="--full without the short `--compute f32` leg whose rate the f32x3 line carries as `strict_fp32`")
     ap.add_argument("--teacher-graph", action="store_true",
                     help="replay the frozen teacher's pass from a hipGraph (BASELINE configs[4]); same arithmetic")
     ap.add_argument("--compute", choices=["f32x3", "f32", "bf16"], default="f32x3",
@@ -456,11 +518,33 @@ def main():
         if not still_held:
             raise SystemExit("bench.py --occupy-cus: the spin kernel ended inside the timed region -- the measurement is void "
                              "(raise the spin length in bench.py for this --steps)")
+    if args.dump_outputs:
+        # the last timed step replayed in steady state from the seeded weights (see the module docstring)
+        j = warm + args.steps - 1
+        model_d, _ = build_model(device, rank, args.arch)
+        tr_d = ERDTrainer(model_d, lr=opt.lr, momentum=opt.momentum, weight_decay=opt.weight_decay,
+                          base_batch_size=cfg.auto_scale_lr.base_batch_size, batch_size_per_gpu=args.batch,
+                          auto_scale_lr=cfg.auto_scale_lr.enable, teacher_graph=args.teacher_graph, step_graph=args.step_graph)
+        if args.serial:                      # (as set_serial does to the timed trainer)
+            tr_d.overlap_teacher = False
+            tr_d.step_graph = False
+        if j > 0:
+            tr_d.iter = j - 1
+            tr_d.train_step(*seq(j - 1), next_batch=nb(j - 1))
+            tr_d.flush()                     # (the update of step j-1 lands before the snapshot; the look-ahead stays queued)
+        idx = dump_index(tr_d)
+        before = param_sample(tr_d, idx)
+        log_d = tr_d.train_step(*seq(j), next_batch=nb(j))
+        tr_d.flush()
+        barrier()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, log_d, tr_d, idx, before)
+        del tr_d, model_d, log_d, before
     rel_area = sum(area(j) for j in range(warm, warm + args.steps)) / args.steps     # mean padded area of the timed steps / 800x1344
     # roofline leg: the same steps again with HIP events around every GEMM-shaped launch, streams serialized
     # (overlapping kernels have no well-defined individual duration).  Not part of `value`.
     ktime, rsteps = None, 0
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         set_serial(True)
         trainer.train_step(*batches[0])
         trainer.flush()
@@ -476,7 +560,7 @@ def main():
     # (`--compute f32`: IEEE fp32 products, the reference's arithmetic, resnet.py:268-300 -> ATen conv), a short leg on a second
     # trainer built under that mode; reported next to `value`, never as `value`
     strict = None
-    if args.compute == "f32x3" and not args.no_strict_fp32 and not args.serial and not args.mixed_res:
+    if args.full and args.compute == "f32x3" and not args.no_strict_fp32 and not args.serial and not args.mixed_res:
         K.set_compute("f32")
         try:
             model2, _ = build_model(device, rank, args.arch)
@@ -678,7 +762,7 @@ def main():
                                   "launches_per_step": r["launches"] // rsteps} for k, r in ktime.items()}
         if strict is not None:
             out["strict_fp32"] = strict
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

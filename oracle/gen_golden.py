@@ -282,12 +282,68 @@ def gen_f10(ref):
     np.savez_compressed(os.path.join(OUT, "f10_head_empty_gt.npz"), **out)
 
 
+def gen_f11(ref):
+    """host-side data: the reference's config files as evaluated dicts, the output of its scripts/select_categories.py on a toy
+    annotation file, and the batches of its AspectRatioBatchSampler on a toy dataset (tests/test_host_boundary.py,
+    tests/test_datasets_cpu.py)"""
+    import importlib.util
+    import json
+    import runpy
+    import tempfile
+    from erd_amd import Config
+    from erd_amd.datasets import CocoAnnotations
+    from test_datasets_cpu import toy_coco
+    from torch.utils.data import Sampler
+    out = {"configs": {}, "select_categories": None, "batch_sampler": {}}
+    for name in G.F11_CONFIGS:
+        d = Config.fromfile(os.path.join(ref_stub.REF_ROOT, "configs", "gfl_increment", name)).to_dict()
+        d.pop("filename")
+        out["configs"][name] = G.json_tagged(d)
+    with tempfile.TemporaryDirectory() as tmp:
+        json.dump(toy_coco(n_cat=80, n_img=200, seed=3), open(os.path.join(tmp, "instances_toy.json"), "w"))
+        argv = sys.argv
+        sys.argv = ["select_categories.py", "--data_path", tmp, "--anno_file", "instances_toy"]
+        try:
+            runpy.run_path(os.path.join(ref_stub.REF_ROOT, "scripts", "select_categories.py"), run_name="__main__")
+        finally:
+            sys.argv = argv
+        out["select_categories"] = json.load(open(os.path.join(tmp, "instances_toy_last_40_cats.json")))
+    reg = sys.modules["mmdet.registry"]
+    if not hasattr(reg, "DATA_SAMPLERS"):
+        class _R:
+            def register_module(self, *a, **k):
+                return lambda c: c
+        reg.DATA_SAMPLERS = _R()
+    spec = importlib.util.spec_from_file_location("_ref_batch_sampler",
+                                                  os.path.join(ref_stub.REF_ROOT, "mmdet/datasets/samplers/batch_sampler.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    a = CocoAnnotations(toy_coco(n_img=61, seed=5), classes=[f"c{i}" for i in range(1, 40, 3)], filter_empty_gt=False, min_size=0)
+
+    class S(Sampler):
+        def __init__(self, order, dataset):
+            self.order, self.dataset = order, dataset
+
+        def __iter__(self):
+            return iter(self.order)
+
+        def __len__(self):
+            return len(self.order)
+
+    for bs, drop_last in G.F11_SAMPLER_CASES:
+        order = [int(i) for i in np.random.RandomState(bs).permutation(len(a))]
+        out["batch_sampler"][f"{bs},{int(drop_last)}"] = {
+            "batches": [[int(i) for i in b] for b in mod.AspectRatioBatchSampler(S(order, a), bs, drop_last)],
+            "len": len(mod.AspectRatioBatchSampler(S(order, a), bs, drop_last))}
+    json.dump(out, open(os.path.join(OUT, "f11_host_data.json"), "w"), sort_keys=True, separators=(",", ":"))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
     ref = ref_stub.load_reference()
     only = set(sys.argv[1:])                 # e.g. `python oracle/gen_golden.py gen_f10`
-    for fn in (gen_f1, gen_f2, gen_f3, gen_f4, gen_f5, gen_f6, gen_f7, gen_f8, gen_f9, gen_f10):
+    for fn in (gen_f1, gen_f2, gen_f3, gen_f4, gen_f5, gen_f6, gen_f7, gen_f8, gen_f9, gen_f10, gen_f11):
         if only and fn.__name__ not in only:
             continue
         fn(ref)

@@ -138,3 +138,29 @@ def f8_inputs(case):
     bbox = [randn(830 + l, N, 68, h, w, scale=2.5) for l, (h, w) in enumerate(sizes)]
     metas = [dict(img_shape=(H, W), pad_shape=(H, W), batch_input_shape=(H, W), scale_factor=(1.0, 1.0))]
     return cls, bbox, metas, False
+
+
+# ---- F11: host-side data of the reference (config files, category selection script, batch sampler) ----------------------
+F11_CONFIGS = ["gfl_r50_fpn_1x_coco_first_40_cats.py", "gfl_r50_fpn_1x_coco_first_40_incre_last_40_cats.py"]
+F11_SAMPLER_CASES = [(2, False), (4, False), (4, True), (7, False)]
+
+
+def json_tagged(obj):
+    """JSON form that keeps tuples apart from lists (a config that turns a tuple into a list is a different config)"""
+    if isinstance(obj, tuple):
+        return {"__tuple__": [json_tagged(v) for v in obj]}
+    if isinstance(obj, list):
+        return [json_tagged(v) for v in obj]
+    if isinstance(obj, dict):
+        return {str(k): json_tagged(v) for k, v in obj.items()}
+    return obj
+
+
+def json_untagged(obj):
+    if isinstance(obj, dict):
+        if set(obj) == {"__tuple__"}:
+            return tuple(json_untagged(v) for v in obj["__tuple__"])
+        return {k: json_untagged(v) for k, v in obj.items()}
+    if isinstance(obj, list):
+        return [json_untagged(v) for v in obj]
+    return obj

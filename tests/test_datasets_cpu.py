@@ -1,10 +1,8 @@
 """CPU: annotation side of the data pipeline -- category slicing and aspect-ratio batching
-against the reference's own code run in this container, COCO parsing/filter rules as known answers
-(mmdet/datasets/coco.py:102-212)."""
-import importlib.util
+against what the reference's own code produced on the same toy data (fixture F11, oracle/gen_golden.py gen_f11), COCO
+parsing/filter rules as known answers (mmdet/datasets/coco.py:102-212)."""
 import json
 import os
-import runpy
 import sys
 
 import numpy as np
@@ -12,8 +10,7 @@ import pytest
 
 from erd_amd.datasets import AspectRatioBatchSampler, CocoAnnotations, rescale_size, select_categories
 
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
+F11 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "f11_host_data.json")
 
 
 def toy_coco(n_img=60, n_cat=12, seed=0):
@@ -33,14 +30,11 @@ def toy_coco(n_img=60, n_cat=12, seed=0):
     return dict(images=images, annotations=annos, categories=cats)
 
 
-@needs_ref
 def test_select_categories_equals_reference_script(tmp_path, monkeypatch):
     ds = toy_coco(n_cat=80, n_img=200, seed=3)
     src = tmp_path / "instances_toy.json"
     json.dump(ds, open(src, "w"))
-    monkeypatch.setattr(sys, "argv", ["select_categories.py", "--data_path", str(tmp_path), "--anno_file", "instances_toy"])
-    runpy.run_path(os.path.join(REF, "scripts", "select_categories.py"), run_name="__main__")   # writes ..._last_40_cats.json
-    want = json.load(open(tmp_path / "instances_toy_last_40_cats.json"))
+    want = json.load(open(F11))["select_categories"]      # the reference's scripts/select_categories.py on this file (..._last_40_cats.json)
     got = select_categories(ds, 40, 80)
     assert got == want
     first = select_categories(ds, 0, 40)
@@ -96,21 +90,11 @@ def test_rescale_size_known_answers():
     assert rescale_size((480, 640), (1333, 800)) == (800, 1067)
 
 
-@needs_ref
 @pytest.mark.parametrize("bs,drop_last", [(2, False), (4, False), (4, True), (7, False)])
 def test_aspect_ratio_batch_sampler_equals_reference_class(bs, drop_last):
-    from oracle import ref_stub
-    ref_stub.load_reference()
-    reg = sys.modules["mmdet.registry"]
-    if not hasattr(reg, "DATA_SAMPLERS"):
-        class _R:
-            def register_module(self, *a, **k):
-                return lambda c: c
-        reg.DATA_SAMPLERS = _R()
-    spec = importlib.util.spec_from_file_location("_ref_batch_sampler", os.path.join(REF, "mmdet/datasets/samplers/batch_sampler.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    """the batches and the length of the reference's AspectRatioBatchSampler on the same sampler order (fixture F11)"""
     from torch.utils.data import Sampler
+    ref = json.load(open(F11))["batch_sampler"][f"{bs},{int(drop_last)}"]
     a = CocoAnnotations(toy_coco(n_img=61, seed=5), classes=[f"c{i}" for i in range(1, 40, 3)], filter_empty_gt=False, min_size=0)
 
     class S(Sampler):
@@ -124,10 +108,10 @@ def test_aspect_ratio_batch_sampler_equals_reference_class(bs, drop_last):
             return len(self.order)
 
     order = [int(i) for i in np.random.RandomState(bs).permutation(len(a))]
-    want = list(mod.AspectRatioBatchSampler(S(order, a), bs, drop_last))
+    want = ref["batches"]
     mine = AspectRatioBatchSampler(S(order, a), a, bs, drop_last)
     assert list(mine) == want
-    assert len(mine) == len(mod.AspectRatioBatchSampler(S(order, a), bs, drop_last))
+    assert len(mine) == ref["len"]
     assert list(mine) == want            # the buckets reset between epochs
 
 

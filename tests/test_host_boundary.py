@@ -1,5 +1,6 @@
 """CPU: the drop-in boundary -- config files, registry, state-dict ABI, teacher load /
 student warm start, C-ABI exports.  No compute: erd_amd has no CPU path (and says so)."""
+import json
 import os
 import re
 import tempfile
@@ -9,10 +10,9 @@ import torch
 
 import erd_amd
 from erd_amd import Config, MODELS, TASK_UTILS
+import golden_inputs as G
 from e2e_util import CFG_FIRST, CFG_INCRE, ROOT
 from oracle import erd_oracle as O
-
-REF_CFG = "/root/reference/configs/gfl_increment"
 
 
 def test_configs_load_and_inherit_bases():
@@ -26,14 +26,15 @@ def test_configs_load_and_inherit_bases():
     assert cfg.train_dataloader.dataset.ann_file.endswith("sel_last_40_cats.json")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference tree only exists in the build container")
 @pytest.mark.parametrize("name", ["gfl_r50_fpn_1x_coco_first_40_cats.py",
                                   "gfl_r50_fpn_1x_coco_first_40_incre_last_40_cats.py"])
 def test_reference_config_files_load_unchanged_and_equal_ours(name):
-    ref = Config.fromfile(os.path.join(REF_CFG, name)).to_dict()
+    """the reference's config files as this Config loader evaluates them (fixture F11, oracle/gen_golden.py gen_f11) equal ours"""
+    stored = json.load(open(os.path.join(ROOT, "tests", "golden", "f11_host_data.json")))["configs"][name]
+    ref = G.json_untagged(stored)
     ours = Config.fromfile(os.path.join(ROOT, "configs", "gfl_increment", name)).to_dict()
-    ref.pop("filename"); ours.pop("filename")
-    assert ref == ours
+    ours.pop("filename")
+    assert G.json_tagged(ours) == stored and ref == ours
     MODELS.build(dict(ref["model"], latest_model_flag=False) if "ori_setting" in ref["model"] else ref["model"])
 
 
