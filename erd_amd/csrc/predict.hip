@@ -412,6 +412,146 @@ __global__ __launch_bounds__(1024) void pred_nms_kernel(const float4* __restrict
     if (threadIdx.x == 0) det_num[n] = s_kept;
 }
 
+// ---- test-time augmentation: merge the views' detections of each image (DetTTAModel._merge_single_sample) --------
+// Per image: the views' valid rows of erd_predict_nms's output gathered in view order, flipped views mirrored back
+// around the original width (bbox_flip, transforms.py:43-46), then batched_nms over the merged set exactly as
+// pred_nms_kernel runs it (class offsets label * (max + 1) in fp32, rank sort score desc / position asc, IoU > thr
+// suppresses), first max_per_img survivors.  The greedy pass keeps the rank-ordered offset boxes, their merged
+// positions and suppression flags in static LDS for K <= TTA_LDS_K (20 views x 100); larger K runs the same
+// decisions out of the global workspace.  ws per image: wb[Kc] float4 (merged boxes), ob[Kc] float4 (offset boxes),
+// rb[Kc] float4 (offset boxes in rank order), sc[Kc], lab[Kc] int, ridx[Kc] int, rrem[Kc] int; Kc = V * P.
+constexpr int TTA_LDS_K = 2048;
+
+template <typename Flag>
+__device__ __forceinline__ void tta_rank_(const float* sc, const float4* ob, int K, float4* rb, int* ridx, Flag* rrem) {
+    for (int i = threadIdx.x; i < K; i += 1024) {
+        const float si = sc[i];
+        int rank = 0;
+        for (int j = 0; j < K; ++j) {
+            const float sj = sc[j];
+            rank += (sj > si || (sj == si && j < i)) ? 1 : 0;
+        }
+        rb[rank] = ob[i];
+        ridx[rank] = i;
+        rrem[rank] = 0;
+    }
+    __syncthreads();
+}
+
+// greedy pass over the rank-ordered boxes; thread 0 writes the survivors' merged boxes.  Returns the kept count.
+template <typename Flag>
+__device__ __forceinline__ int tta_greedy_(const float4* rb, const int* ridx, Flag* rrem, int K, const float4* wb,
+                                           const float* sc, const int* lab, float iou_thr, int max_per_img,
+                                           float* dets, int64_t* det_labels, int* s_kept) {
+    for (int oi = 0; oi < K; ++oi) {
+        if (rrem[oi]) continue;                 // uniform: every thread reads the same flag after the last barrier
+        const int kept_now = *s_kept + 1;       // read before the barrier, written after it
+        if (threadIdx.x == 0) {
+            const int i = ridx[oi];
+            const float4 b = wb[i];
+            float* d = dets + (int64_t)(kept_now - 1) * 5;
+            d[0] = b.x; d[1] = b.y; d[2] = b.z; d[3] = b.w; d[4] = sc[i];
+            det_labels[kept_now - 1] = lab[i];
+        }
+        const float4 bi = rb[oi];
+        const float ai = (bi.z - bi.x) * (bi.w - bi.y);
+        if (kept_now < max_per_img) {
+            for (int oj = oi + 1 + threadIdx.x; oj < K; oj += 1024) {
+                if (rrem[oj]) continue;
+                const float4 bj = rb[oj];
+                const float w = fmaxf(fminf(bi.z, bj.z) - fmaxf(bi.x, bj.x), 0.f);
+                const float h = fmaxf(fminf(bi.w, bj.w) - fmaxf(bi.y, bj.y), 0.f);
+                const float inter = w * h;
+                const float aj = (bj.z - bj.x) * (bj.w - bj.y);
+                const float iou = inter / (ai + aj - inter);
+                if (iou > iou_thr) rrem[oj] = 1;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) *s_kept = kept_now;
+        __syncthreads();
+        if (kept_now >= max_per_img) break;
+    }
+    return *s_kept;
+}
+
+__global__ __launch_bounds__(1024) void tta_merge_kernel(const float* __restrict__ dets, const int64_t* __restrict__ labels,
+                                                         const int32_t* __restrict__ num, int V, int N, int P,
+                                                         const int32_t* __restrict__ flip, const float* __restrict__ ori_w,
+                                                         float iou_thr, int max_per_img, float* __restrict__ out_dets,
+                                                         int64_t* __restrict__ out_labels, int32_t* __restrict__ out_num,
+                                                         float* __restrict__ ws) {
+    __shared__ float red[16];
+    __shared__ int s_kept;
+    __shared__ float4 s_rb[TTA_LDS_K];         // 32 + 8 + 8 + 2 KB: the greedy pass of K <= TTA_LDS_K boxes runs out of LDS
+    __shared__ float s_sc[TTA_LDS_K];
+    __shared__ int s_ridx[TTA_LDS_K];
+    __shared__ uint8_t s_rem[TTA_LDS_K];
+    const int n = blockIdx.x;
+    const int Kc = V * P;
+    float4* wb = reinterpret_cast<float4*>(ws + (int64_t)n * Kc * 16);
+    float4* ob = wb + Kc;
+    float4* rb = ob + Kc;
+    float* sc = reinterpret_cast<float*>(rb + Kc);
+    int* lab = reinterpret_cast<int*>(sc + Kc);
+    int* ridx = lab + Kc;
+    int* rrem = ridx + Kc;
+    const float W = ori_w[n];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // gather in view order (torch.cat of the views' results), each view in its own order; un-flip around W
+    int K = 0;
+    float lmax = -INFINITY;
+    for (int v = 0; v < V; ++v) {
+        const int m = min(max(num[(int64_t)v * N + n], 0), P);
+        const int64_t row = (int64_t)v * N + n;
+        const bool fl = flip[v] != 0;
+        for (int j = threadIdx.x; j < m; j += 1024) {
+            const float* d = dets + (row * P + j) * 5;
+            float4 b = make_float4(d[0], d[1], d[2], d[3]);
+            if (fl) {
+                const float x1 = W - b.z, x2 = W - b.x;
+                b.x = x1; b.z = x2;
+            }
+            wb[K + j] = b;
+            sc[K + j] = d[4];
+            lab[K + j] = (int)labels[row * P + j];
+            lmax = fmaxf(lmax, fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)));
+        }
+        K += m;
+    }
+    if (K == 0) {                               // nothing merged: the reference returns view 0's (empty) result
+        if (threadIdx.x == 0) out_num[n] = 0;
+        return;
+    }
+    lmax = erd::wave_max(lmax);
+    if (lane == 0) red[wave] = lmax;
+    if (threadIdx.x == 0) s_kept = 0;
+    __syncthreads();
+    float maxc = red[0];
+    for (int i = 1; i < 16; ++i) maxc = fmaxf(maxc, red[i]);
+    const float offs = maxc + 1.0f;             // boxes.max() + 1 (batched_nms)
+    for (int i = threadIdx.x; i < K; i += 1024) {
+        const float o = (float)lab[i] * offs;
+        float4 b = wb[i];
+        b.x += o; b.y += o; b.z += o; b.w += o;
+        ob[i] = b;
+    }
+    __syncthreads();
+    float* od = out_dets + (int64_t)n * max_per_img * 5;
+    int64_t* ol = out_labels + (int64_t)n * max_per_img;
+    int kept;
+    if (K <= TTA_LDS_K) {
+        for (int i = threadIdx.x; i < K; i += 1024) s_sc[i] = sc[i];
+        __syncthreads();
+        tta_rank_(s_sc, ob, K, s_rb, s_ridx, s_rem);
+        kept = tta_greedy_(s_rb, s_ridx, s_rem, K, wb, sc, lab, iou_thr, max_per_img, od, ol, &s_kept);
+    } else {
+        tta_rank_(sc, ob, K, rb, ridx, rrem);
+        kept = tta_greedy_(rb, ridx, rrem, K, wb, sc, lab, iou_thr, max_per_img, od, ol, &s_kept);
+    }
+    if (threadIdx.x == 0) out_num[n] = kept;
+}
+
 inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 }  // namespace
@@ -483,4 +623,20 @@ extern "C" int erd_predict_nms(const float* boxes, const float* scores, const in
                        reinterpret_cast<const float4*>(boxes), scores, labels, num, max_cols, inv_scale, min_bbox_size,
                        iou_thr, max_per_img, dets, det_labels, det_num, reinterpret_cast<float*>(ws));
     return erd::check_launch("predict_nms");
+}
+
+extern "C" size_t erd_tta_merge_ws_bytes(int V, int N, int P) {
+    return (size_t)N * V * P * 16 * sizeof(float);
+}
+
+extern "C" int erd_tta_merge(const float* dets, const int64_t* labels, const int32_t* num, int V, int N, int P,
+                             const int32_t* flip, const float* ori_w, float iou_thr, int max_per_img, float* out_dets,
+                             int64_t* out_labels, int32_t* out_num, void* ws, size_t ws_bytes, erd_stream_t stream) {
+    ERD_REQUIRE(dets && labels && num && flip && ori_w && out_dets && out_labels && out_num && ws, "tta_merge: null");
+    ERD_REQUIRE(V > 0 && N > 0 && P > 0 && max_per_img > 0, "tta_merge: bad sizes");
+    ERD_REQUIRE((int64_t)V * P < (1ll << 26), "tta_merge: too many candidates per image");
+    ERD_REQUIRE(ws_bytes >= erd_tta_merge_ws_bytes(V, N, P), "tta_merge: workspace too small");
+    hipLaunchKernelGGL(tta_merge_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, dets, labels, num, V, N, P, flip,
+                       ori_w, iou_thr, max_per_img, out_dets, out_labels, out_num, reinterpret_cast<float*>(ws));
+    return erd::check_launch("tta_merge");
 }

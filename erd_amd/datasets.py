@@ -12,6 +12,7 @@ from __future__ import annotations
 import json
 import math
 import os
+import warnings
 from collections import defaultdict
 from typing import Dict, Iterable, Iterator, List, Optional, Sequence
 
@@ -266,3 +267,102 @@ class GpuDetPipeline:
             s.set_metainfo(dict(pad_shape=(H, W), batch_input_shape=(H, W)))
             samples.append(s)
         return out, samples
+
+    def assemble_tta(self, indices: Sequence[int], imgs: Sequence[np.ndarray], scales, flips):
+        """TestTimeAug of one decoded batch: the views (scale s, flip f) of the N images in product order, scale
+        outermost -- the order DetTTAModel merges them in.  Each image goes to the device once; the views of one scale
+        share one padded [len(flips)*N,3,H,W] batch, view f being rows f*N..(f+1)*N-1.
+        Returns [(inputs [N,3,H,W], data samples)] per view."""
+        from . import kernels as K
+        N = len(imgs)
+        srcs = [(im if isinstance(im, torch.Tensor) else torch.from_numpy(im)).to(self.device, non_blocking=True)
+                for im in imgs]
+        views = []
+        for scale in scales:
+            new = [rescale_size((im.shape[1], im.shape[0]), tuple(scale)) for im in imgs]          # (w, h)
+            H = max(int(math.ceil(h / self.div)) * self.div for _, h in new)
+            W = max(int(math.ceil(w / self.div)) * self.div for w, _ in new)
+            out = torch.empty((len(flips) * N, 3, H, W), dtype=torch.float32, device=self.device)
+            for f, flip in enumerate(flips):
+                samples = []
+                for k, (i, im, (nw, nh)) in enumerate(zip(indices, imgs, new)):
+                    K.resize_normalize_into(srcs[k], self._table(im.shape[0], im.shape[1], nh, nw), (nh, nw), out[f * N + k],
+                                            self.mean, self.std, bool(flip), self.swap, self.pad_value)
+                    s = self.ann.data_sample(i, scale_factor=(nw / im.shape[1], nh / im.shape[0]), flip=bool(flip),
+                                             img_shape=(nh, nw), clip=True)
+                    s.set_metainfo(dict(pad_shape=(H, W), batch_input_shape=(H, W),
+                                        flip_direction="horizontal" if flip else None))
+                    samples.append(s)
+                views.append((out[f * N:(f + 1) * N], samples))
+        return views
+
+
+DEFAULT_TTA_MODEL = dict(type="DetTTAModel", tta_cfg=dict(nms=dict(type="nms", iou_threshold=0.5), max_per_img=100))
+
+
+def _test_dataset_cfg(cfg) -> dict:
+    d = cfg["test_dataloader"]["dataset"]
+    while "dataset" in d:
+        d = d["dataset"]
+    return d
+
+
+def _resize_scale(t: dict) -> tuple:
+    if not t.get("keep_ratio", False) or t.get("scale") is None or len(t["scale"]) != 2:
+        raise ValueError(f"--tta: only Resize(scale=(w, h), keep_ratio=True) is built, got {dict(t)}")
+    return tuple(int(v) for v in t["scale"])
+
+
+def _flip_of(t: dict) -> bool:
+    prob, direction = t.get("prob"), t.get("direction", "horizontal")
+    if direction != "horizontal" or prob not in (0, 1):
+        raise ValueError(f"--tta: only RandomFlip(prob=1.) / RandomFlip(prob=0.), horizontal, is built, got {dict(t)}")
+    return bool(prob == 1)
+
+
+def resolve_tta(cfg) -> dict:
+    """tools/test.py --tta (reference tools/test.py:93-120): the config's `tta_model` / `tta_pipeline`, or the flip-only
+    defaults (with the reference's warnings) at the scale of the test pipeline's Resize.  The pipeline is read, not run:
+    a TestTimeAug whose lists are Resize(keep_ratio=True) scales and RandomFlip probs 1 / 0 (configs/retinanet/
+    retinanet_tta.py's form), around LoadImageFromFile / LoadAnnotations / PackDetInputs.  Anything else raises.
+    Returns dict(tta_model=..., scales=[(w, h), ...], flips=[bool, ...]); the views are their product, scale outermost."""
+    tta_model = cfg.get("tta_model")
+    if tta_model is None:
+        warnings.warn("Cannot find ``tta_model`` in config, we will set it as default.")
+        tta_model = DEFAULT_TTA_MODEL
+    tta_model = json.loads(json.dumps(tta_model))                  # plain dicts, the config stays untouched
+    if tta_model.get("type") != "DetTTAModel":
+        raise ValueError(f"--tta: tta_model type {tta_model.get('type')!r} is not built (DetTTAModel is)")
+    test_resize = [t for t in _test_dataset_cfg(cfg).get("pipeline", []) if t.get("type") == "Resize"]
+    base = _resize_scale(test_resize[0]) if test_resize else (1333, 800)
+    pipeline = cfg.get("tta_pipeline")
+    if pipeline is None:
+        warnings.warn("Cannot find ``tta_pipeline`` in config, we will set it as default.")
+        return dict(tta_model=tta_model, scales=[base], flips=[True, False])
+    scales, flips, outer, tta = None, None, None, False
+    for t in pipeline:
+        kind = t.get("type")
+        if kind in ("LoadImageFromFile", "LoadAnnotations", "PackDetInputs"):
+            continue
+        if kind == "Resize" and not tta:
+            outer = _resize_scale(t)
+        elif kind == "TestTimeAug" and not tta:
+            tta = True
+            for group in t["transforms"]:
+                kinds = {g.get("type") for g in group}
+                if kinds == {"Resize"}:
+                    if scales is not None or outer is not None:
+                        raise ValueError("--tta: more than one Resize stage in tta_pipeline")
+                    scales = [_resize_scale(g) for g in group]
+                elif kinds == {"RandomFlip"}:
+                    if flips is not None:
+                        raise ValueError("--tta: more than one RandomFlip stage in tta_pipeline")
+                    flips = [_flip_of(g) for g in group]
+                elif not kinds or not kinds <= {"LoadAnnotations", "PackDetInputs"}:
+                    raise ValueError(f"--tta: TestTimeAug transform list {sorted(map(str, kinds))} is not built "
+                                     "(Resize(keep_ratio=True) scales and RandomFlip probs 1 / 0 are)")
+        else:
+            raise ValueError(f"--tta: tta_pipeline transform {kind!r} is not built")
+    if not tta:
+        raise ValueError("--tta: tta_pipeline has no TestTimeAug")
+    return dict(tta_model=tta_model, scales=scales or [outer or base], flips=flips or [False])

@@ -1376,19 +1376,50 @@ def predict_topk(cls: Tensor, bbox: Tensor, anchors: Tensor, sizes, strides, img
 
 
 def predict_nms(boxes: Tensor, scores: Tensor, labels: Tensor, num: Tensor, inv_scale: Tensor, min_bbox_size: float,
-                iou_thr: float, max_per_img: int):
+                iou_thr: float, max_per_img: int, out=None):
     """rescale + size filter + class-offset NMS + top max_per_img (base_dense_head.py:424-486).
-    Returns dets [N, max_per_img, 5], det_labels [N, max_per_img] (int64), det_num [N] (int32)."""
+    Returns dets [N, max_per_img, 5], det_labels [N, max_per_img] (int64), det_num [N] (int32); `out` = those three
+    (contiguous, rows past each count zero) to write into instead of new buffers."""
     N, cols, _ = boxes.shape
     dev = boxes.device
-    dets = torch.zeros((N, max_per_img, 5), dtype=torch.float32, device=dev)
-    det_labels = torch.zeros((N, max_per_img), dtype=torch.int64, device=dev)
-    det_num = torch.empty((N,), dtype=torch.int32, device=dev)
+    if out is None:
+        dets = torch.zeros((N, max_per_img, 5), dtype=torch.float32, device=dev)
+        det_labels = torch.zeros((N, max_per_img), dtype=torch.int64, device=dev)
+        det_num = torch.empty((N,), dtype=torch.int32, device=dev)
+    else:
+        dets, det_labels, det_num = out
+        assert dets.shape == (N, max_per_img, 5) and det_labels.shape == (N, max_per_img) and det_num.shape == (N,)
+        assert dets.dtype == torch.float32 and det_labels.dtype == torch.int64 and det_num.dtype == torch.int32
+        assert dets.is_contiguous() and det_labels.is_contiguous() and det_num.is_contiguous()
     nbytes = N * cols * 48
     ws = workspace("predict_nms", nbytes, dev)
     call("erd_predict_nms", _p(boxes), _p(scores), _p(labels), _p(num), N, cols, _p(inv_scale), float(min_bbox_size),
          float(iou_thr), int(max_per_img), _p(dets), _p(det_labels), _p(det_num), _p(ws), C.c_size_t(nbytes), _stream())
     return dets, det_labels, det_num
+
+
+def tta_merge(dets: Tensor, labels: Tensor, num: Tensor, flip, ori_w, iou_thr: float, max_per_img: int):
+    """test-time augmentation: merge the views of every image (DetTTAModel._merge_single_sample).  dets [V, N, P, 5],
+    labels [V, N, P] (int64), num [V, N] (int32) are predict_nms's outputs, view-major; flip: V flags (horizontal
+    flip of the view), ori_w: N original image widths.  Returns dets [N, max_per_img, 5], labels [N, max_per_img]
+    (int64), num [N] (int32)."""
+    _require_gpu(dets, labels, num)
+    V, N, P, _ = dets.shape
+    assert dets.dtype == torch.float32 and labels.dtype == torch.int64 and num.dtype == torch.int32
+    assert labels.shape == (V, N, P) and num.shape == (V, N) and len(flip) == V and len(ori_w) == N
+    dets, labels, num = dets.contiguous(), labels.contiguous(), num.contiguous()
+    dev = dets.device
+    fl = torch.tensor([1 if f else 0 for f in flip], dtype=torch.int32).to(dev, non_blocking=True)
+    ow = (ori_w.to(dev, torch.float32) if isinstance(ori_w, Tensor)
+          else torch.tensor([float(w) for w in ori_w], dtype=torch.float32).to(dev, non_blocking=True))
+    out_dets = torch.zeros((N, max_per_img, 5), dtype=torch.float32, device=dev)
+    out_labels = torch.zeros((N, max_per_img), dtype=torch.int64, device=dev)
+    out_num = torch.empty((N,), dtype=torch.int32, device=dev)
+    nbytes = int(_lib.load().erd_tta_merge_ws_bytes(V, N, P))
+    ws = workspace("tta_merge", nbytes, dev)
+    call("erd_tta_merge", _p(dets), _p(labels), _p(num), V, N, P, _p(fl), _p(ow), float(iou_thr), int(max_per_img),
+         _p(out_dets), _p(out_labels), _p(out_num), _p(ws), C.c_size_t(nbytes), _stream())
+    return out_dets, out_labels, out_num
 
 
 def kd_kl(s_bbox, t_bbox, s_cls, keep, c_old, T):

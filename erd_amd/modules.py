@@ -751,11 +751,28 @@ class GFLHead(nn.Module):
         (base_dense_head.py:201-289,424-486; gfl_head.py:408-502) for the whole batch on the GPU: two C-ABI calls
         (erd_predict_topk, erd_predict_nms), one device->host copy of the N detection counts at the end."""
         _gpu_only(cls, "GFLHead.predict_by_feat")
+        if (self.test_cfg if cfg is None else cfg) is not None and not with_nms:
+            raise NotImplementedError("with_nms=False is the test-time-augmentation path (out of scope)")
+        dets, det_labels, det_num = self.predict_padded_cat(cls, bbox, sizes, batch_img_metas, cfg, rescale)
+        counts = det_num.tolist()
+        out = []
+        for n in range(cls.shape[0]):
+            r = InstanceData()
+            r.bboxes = dets[n, :counts[n], :4]
+            r.scores = dets[n, :counts[n], 4]
+            r.labels = det_labels[n, :counts[n]]
+            out.append(r)
+        return out
+
+    def predict_padded_cat(self, cls: Tensor, bbox: Tensor, sizes, batch_img_metas, cfg=None, rescale: bool = False,
+                           out=None):
+        """the device half of `predict_by_feat_cat`: predict_nms's padded buffers dets [N, max_per_img, 5], labels
+        [N, max_per_img] (int64), num [N] (int32), with no host synchronisation.  `out`: those three to write into
+        (DetTTAModel hands in slices of its view-major buffers)."""
+        _gpu_only(cls, "GFLHead.predict_by_feat")
         cfg = self.test_cfg if cfg is None else cfg
         if cfg is None:
             raise ValueError("predict needs a test_cfg (nms_pre, score_thr, nms, max_per_img)")
-        if not with_nms:
-            raise NotImplementedError("with_nms=False is the test-time-augmentation path (out of scope)")
         nms = dict(cfg["nms"])
         if nms.get("type", "nms") != "nms" or nms.get("class_agnostic", False):
             raise NotImplementedError("only class-aware hard NMS (the ERD configs) is built")
@@ -777,17 +794,8 @@ class GFLHead(nn.Module):
         strides = list(self.prior_generator.strides)
         boxes, scores, labels, num = K.predict_topk(cls.contiguous(), bbox.contiguous(), anchors, sizes, strides, hw,
                                                     float(cfg["score_thr"]), nms_pre)
-        dets, det_labels, det_num = K.predict_nms(boxes, scores, labels, num, inv, float(cfg.get("min_bbox_size", -1)),
-                                                  float(nms["iou_threshold"]), int(cfg["max_per_img"]))
-        counts = det_num.tolist()
-        out = []
-        for n in range(N):
-            r = InstanceData()
-            r.bboxes = dets[n, :counts[n], :4]
-            r.scores = dets[n, :counts[n], 4]
-            r.labels = det_labels[n, :counts[n]]
-            out.append(r)
-        return out
+        return K.predict_nms(boxes, scores, labels, num, inv, float(cfg.get("min_bbox_size", -1)),
+                             float(nms["iou_threshold"]), int(cfg["max_per_img"]), out=out)
 
     def predict_by_feat(self, cls_scores: Sequence[Tensor], bbox_preds: Sequence[Tensor], score_factors=None,
                         batch_img_metas=None, cfg=None, rescale: bool = False, with_nms: bool = True):
@@ -1160,6 +1168,101 @@ class GFLIncrementERD(GFL):
             s_cls, s_bbox, sizes = self._forward_cat(batch_inputs, trunk=t.trunk)
         return self.bbox_head.loss_cat(t.t_cls, t.t_bbox, s_cls, s_bbox, sizes, batch_data_samples, t.ers, t.keep,
                                        self.ori_num_classes, self.dist_loss_weight, targets=t.targets)
+
+
+@MODELS.register_module()
+class DetTTAModel(nn.Module):
+    """DetTTAModel (test_time_augs/det_tta.py) with mmengine's BaseTTAModel shape: `module` is the detector (a config
+    built through MODELS, or a module), `tta_cfg` = dict(nms=dict(type='nms', iou_threshold=...), max_per_img=...).
+    `predict(views)` takes the view batches of one batch of N images -- (inputs [N,3,H,W], data samples) pairs in the
+    order TestTimeAug makes them -- and returns N data samples (view 0's) whose pred_instances are the merged
+    detections.  Consecutive views of one padded shape run as one forward (both flips of a scale: 2N images), and
+    predict_nms writes straight into view-major buffers; one erd_tta_merge launch merges every image, one device->host
+    copy of the N counts ends the batch."""
+
+    def __init__(self, module, tta_cfg=None, data_preprocessor=None):
+        super().__init__()
+        self.module = MODELS.build(module) if isinstance(module, dict) else module
+        self.tta_cfg = ConfigDict(tta_cfg or {})
+        nms = dict(self.tta_cfg.get("nms") or {})
+        if nms.get("type", "nms") != "nms" or nms.get("class_agnostic", False):
+            raise NotImplementedError("DetTTAModel: only class-aware hard NMS (tta_cfg.nms type='nms') is built")
+        if "iou_threshold" not in nms or "max_per_img" not in self.tta_cfg:
+            raise ValueError("DetTTAModel needs tta_cfg=dict(nms=dict(type='nms', iou_threshold=...), max_per_img=...)")
+
+    @staticmethod
+    def _view(v):
+        return (v["inputs"], v["data_samples"]) if isinstance(v, dict) else (v[0], v[1])
+
+    @staticmethod
+    def _stacked(xs: Sequence[Tensor]) -> Tensor:
+        """the group's inputs as one [k*N,3,H,W] batch: a view of their storage when they lie back to back in it"""
+        a = xs[0]
+        n = a.numel()
+        if a.is_contiguous() and all(x.is_contiguous() and x.untyped_storage().data_ptr() == a.untyped_storage().data_ptr()
+                                     and x.storage_offset() == a.storage_offset() + k * n for k, x in enumerate(xs)):
+            return a.as_strided((len(xs) * a.shape[0],) + tuple(a.shape[1:]), a.stride(), a.storage_offset())
+        return torch.cat(list(xs), 0)
+
+    def predict(self, views) -> List[DetDataSample]:
+        views = [self._view(v) for v in views]
+        V, N = len(views), len(views[0][1])
+        head = self.module.bbox_head
+        P = int(head.test_cfg["max_per_img"])
+        dev = views[0][0].device
+        ori_w, flips = [], []
+        for x, samples in views:
+            if len(samples) != N or x.shape[0] != N:
+                raise ValueError("DetTTAModel: every view holds the same N images")
+        for v, (_, samples) in enumerate(views):
+            ms = [d.metainfo for d in samples]
+            if any(m.get("flip", False) and m.get("flip_direction", "horizontal") != "horizontal" for m in ms):
+                raise NotImplementedError("DetTTAModel: only horizontal flips are built")
+            fl = {bool(m.get("flip", False)) for m in ms}
+            if len(fl) != 1:
+                raise ValueError("DetTTAModel: a view flips all of its images or none")
+            flips.append(fl.pop())
+            w = [float(m["ori_shape"][1]) for m in ms]
+            if v and w != ori_w:
+                raise ValueError("DetTTAModel: the views of one batch hold the same images in the same order")
+            ori_w = w
+        dets = torch.zeros((V, N, P, 5), dtype=torch.float32, device=dev)
+        labels = torch.zeros((V, N, P), dtype=torch.int64, device=dev)
+        num = torch.empty((V, N), dtype=torch.int32, device=dev)
+        with torch.no_grad():
+            v0 = 0
+            while v0 < V:
+                v1 = v0 + 1
+                while v1 < V and views[v1][0].shape == views[v0][0].shape:
+                    v1 += 1
+                x = self._stacked([views[v][0] for v in range(v0, v1)])
+                metas = [d.metainfo for v in range(v0, v1) for d in views[v][1]]
+                cls, bbox, sizes = self.module._forward_cat(x)
+                k = v1 - v0
+                head.predict_padded_cat(cls, bbox, sizes, metas, rescale=True,
+                                        out=(dets[v0:v1].view(k * N, P, 5), labels[v0:v1].view(k * N, P),
+                                             num[v0:v1].view(k * N)))
+                v0 = v1
+            md, ml, mn = K.tta_merge(dets, labels, num, flips, ori_w, float(self.tta_cfg["nms"]["iou_threshold"]),
+                                     int(self.tta_cfg["max_per_img"]))
+        counts = mn.tolist()
+        out = []
+        for n, d in enumerate(views[0][1]):
+            r = InstanceData()
+            r.bboxes = md[n, :counts[n], :4]
+            r.scores = md[n, :counts[n], 4]
+            r.labels = ml[n, :counts[n]]
+            d.pred_instances = r
+            out.append(d)
+        return out
+
+    def test_step(self, views) -> List[DetDataSample]:
+        return self.predict(views)
+
+    def forward(self, views, mode: str = "predict"):
+        if mode != "predict":
+            raise RuntimeError(f'DetTTAModel runs mode="predict" only (got "{mode}")')
+        return self.predict(views)
 
 
 class TeacherOut:

@@ -432,6 +432,17 @@ int erd_predict_nms(const float* boxes, const float* scores, const int32_t* labe
                     int N, int max_cols, const float* inv_scale, float min_bbox_size, float iou_thr,
                     int max_per_img, float* dets, int64_t* det_labels, int32_t* det_num, void* ws,
                     size_t ws_bytes, erd_stream_t stream);
+/* test-time augmentation, DetTTAModel._merge_single_sample (test_time_augs/det_tta.py) for a whole batch, one workgroup
+ * per image: the views' erd_predict_nms outputs, view-major -- dets [V][N][P][5], labels [V][N][P] int64, num [V][N] --
+ * gathered per image in view order, the views with flip[v] != 0 mirrored back around ori_w[n] (x1' = W - x2,
+ * x2' = W - x1: bbox_flip, horizontal), then batched_nms as erd_predict_nms runs it (class offsets in fp32, IoU > iou_thr
+ * suppresses; UNPINNED vs mmcv), first max_per_img survivors.  flip [V] int32 and ori_w [N] live on the device.
+ * Same output layout as erd_predict_nms; an image with no row in any view gets out_num = 0.
+ * ws: erd_tta_merge_ws_bytes(V, N, P) bytes. */
+size_t erd_tta_merge_ws_bytes(int V, int N, int P);
+int erd_tta_merge(const float* dets, const int64_t* labels, const int32_t* num, int V, int N, int P,
+                  const int32_t* flip, const float* ori_w, float iou_thr, int max_per_img, float* out_dets,
+                  int64_t* out_labels, int32_t* out_num, void* ws, size_t ws_bytes, erd_stream_t stream);
 
 /* ---- stand-alone leaf operators: what the registered loss / coder / assigner MODULES run when a caller invokes them
  * directly (the training step itself uses the fused erd_gfl_losses_* / erd_kd_kl* kernels above).  Row-parallel; every

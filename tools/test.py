@@ -2,10 +2,16 @@
 """Evaluate a detector checkpoint: COCO bbox mAP (+ the old / new class split of an incremental run).
 
     python tools/test.py CONFIG CHECKPOINT [--cfg-options k=v ...] [--old-classes 40] [--batch-size 4] [--out results.json]
+                         [--tta]
 
 Reference: tools/test.py + CocoMetric (mmdet/evaluation/metrics/coco_metric.py); the images go through the GPU
 pipeline without flipping, detections are rescaled to the original image (`rescale=True`), the metric is
-erd_amd.evaluation.CocoBBoxEval (COCOeval restated, unpinned)."""
+erd_amd.evaluation.CocoBBoxEval (COCOeval restated, unpinned).
+
+--tta (reference tools/test.py:93-120): the detector runs inside DetTTAModel on every view the config's tta_pipeline
+makes (scales x horizontal flips; without tta_model / tta_pipeline the flip-only defaults at the test Resize scale) and
+the views' detections are merged per image on the GPU (erd_tta_merge).  `--cfg-options test_evaluator.classwise=True`
+prints the class-wise AP table as CocoMetric(classwise=True) does."""
 import argparse
 import json
 import os
@@ -26,12 +32,13 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=4)
     ap.add_argument("--max-images", type=int, default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--tta", action="store_true", help="test-time augmentation (tta_model / tta_pipeline of the config)")
     a = ap.parse_args(argv)
 
     import torch
     from train import parse_cfg_options
     from erd_amd import Config, MODELS
-    from erd_amd.datasets import CocoAnnotations, GpuDetPipeline
+    from erd_amd.datasets import CocoAnnotations, GpuDetPipeline, resolve_tta
     from erd_amd.evaluation import CocoBBoxEval, split_map
     from erd_amd.runner import load_checkpoint
 
@@ -39,15 +46,17 @@ def main(argv=None):
     cfg.merge_from_dict(parse_cfg_options(a.cfg_options))
     if cfg.model.get("latest_model_flag") is not None:
         cfg.model.latest_model_flag = False            # the checkpoint carries the teacher copy (or none is needed to test)
-    model = MODELS.build(cfg.model).cuda().eval()
-    own = model.state_dict()
+    tta = resolve_tta(cfg) if a.tta else None
+    model = MODELS.build(cfg.model if tta is None else dict(tta["tta_model"], module=cfg.model)).cuda().eval()
+    detector = model if tta is None else model.module                                # the checkpoint's weights go here
+    own = detector.state_dict()
     sd = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     sd = sd.get("state_dict", sd)
     sd = {k: v for k, v in sd.items() if k in own}                                   # a student-only test ignores ori_model.*
     missing = [k for k in own if k not in sd and not k.startswith("ori_model.")]
     if missing:
         raise RuntimeError(f"checkpoint lacks {len(missing)} tensors, e.g. {missing[:3]}")
-    model.load_state_dict({**{k: v for k, v in own.items() if k not in sd}, **sd}, strict=True)
+    detector.load_state_dict({**{k: v for k, v in own.items() if k not in sd}, **sd}, strict=True)
 
     dcfg = cfg.test_dataloader.dataset
     root = dcfg.get("data_root", "")
@@ -63,8 +72,11 @@ def main(argv=None):
     batches = [list(range(b0, min(n, b0 + a.batch_size))) for b0 in range(0, n, a.batch_size)]
     decode = lambda idx: (idx, [pinned(im) for im in pipe.decode(idx)])
     for idx, imgs in prefetch_map(decode, batches, int(cfg.test_dataloader.get("num_workers", 0)), 2):
-        x, samples = pipe.assemble(idx, imgs)
-        out = model(x, samples, mode="predict")
+        if tta is None:
+            x, samples = pipe.assemble(idx, imgs)
+            out = model(x, samples, mode="predict")
+        else:
+            out = model(pipe.assemble_tta(idx, imgs, tta["scales"], tta["flips"]), mode="predict")
         for i, d in zip(idx, out):
             p = d.pred_instances
             img_id = ann.get_data_info(i)["img_id"]
@@ -78,6 +90,10 @@ def main(argv=None):
         stats.update(split_map(ev, ann.cat_ids[:n_old]))
     for k, v in stats.items():
         print(f"{k:12s} {v:.4f}")
+    if (cfg.get("test_evaluator") or {}).get("classwise", False):
+        print(f"{'category':24s} mAP")
+        for name, v in ev.classwise().items():
+            print(f"{str(name):24s} {v:.4f}")
     if a.out:
         json.dump(dict(stats=stats, classwise=ev.classwise(), results=results), open(a.out, "w"))
     return stats
