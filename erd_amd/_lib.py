@@ -131,6 +131,9 @@ _SIGNATURES = {
     "erd_predict_nms": [P, P, P, P, i32, i32, P, f32, f32, i32, P, P, P, P, C.c_size_t, P],
     "erd_tta_merge_ws_bytes": [i32, i32, i32],
     "erd_tta_merge": [P, P, P, i32, i32, i32, P, P, f32, i32, P, P, P, P, C.c_size_t, P],
+    "erd_coco_dets_append": [P, P, P, P, i32, i32, P, P, P, P, P],
+    "erd_coco_eval_ws_bytes": [i64, i32, i32, i64],
+    "erd_coco_eval": [P, P, P, P, i64, P, P, P, P, i32, i32, i64, P, P, P, P, P, P, P, P, C.c_size_t, P],
     "erd_qfl_rows": [P, P, P, i64, i32, P, P],
     "erd_qfl_bwd": [P, P, P, P, i64, i32, P, P],
     "erd_dfl": [P, P, P, i64, i32, P, P, P],

@@ -54,6 +54,22 @@ def all_reduce_sum_(tensor: torch.Tensor, async_op: bool = False):
     return dist.all_reduce(tensor, op=dist.ReduceOp.SUM, async_op=async_op)
 
 
+
+def all_gather_stacked(tensor: torch.Tensor) -> torch.Tensor:
+    """[world, *tensor.shape]: every rank's tensor (same shape on every rank), rank order.  RCCL gathers on the device; gloo + GPU
+    tensor stages through host memory as all_reduce_sum_ does."""
+    world = world_size()
+    if world == 1:
+        return tensor.unsqueeze(0)
+    if host_staged(tensor):
+        h = tensor.detach().to("cpu").contiguous()
+        parts = [torch.empty_like(h) for _ in range(world)]
+        dist.all_gather(parts, h)
+        return torch.stack(parts).to(tensor.device)
+    out = torch.empty((world, *tensor.shape), dtype=tensor.dtype, device=tensor.device)
+    dist.all_gather_into_tensor(out, tensor.contiguous())
+    return out
+
 def reduce_mean(tensor: torch.Tensor) -> torch.Tensor:
     """`reduce_mean` of the reference: the mean over ranks as divide-by-world then all-reduce(SUM); the identity when no
     process group is initialised (dist_utils.py:61-62 -- which is how every single-process head test runs).  The ERD head

@@ -9,6 +9,9 @@ area; a match to an ignored ground truth makes the detection ignored); ground tr
 ignored, unmatched detections outside the range are ignored too; precision is made monotone and sampled at 101 recall
 points.  **Unpinned** against pycocotools (no copy to run here): `tests/test_evaluation_cpu.py` holds known answers
 instead.  Host-side numpy, as in the reference.
+
+CocoBBoxEvalGPU computes the same arrays on the GPU (HIP, erd_amd/csrc/coco_eval.hip), pinned bit for bit to this host
+restatement (tests/test_gpu_coco_eval.py).
 """
 from __future__ import annotations
 
@@ -35,6 +38,26 @@ def _iou_xywh(d: np.ndarray, g: np.ndarray, crowd: np.ndarray) -> np.ndarray:
     da, ga = d[:, 2] * d[:, 3], g[:, 2] * g[:, 3]
     union = np.where(crowd[None, :], da[:, None], da[:, None] + ga[None, :] - inter)
     return inter / np.maximum(union, 1e-12)
+
+
+def coco_stats(precision: np.ndarray, recall: np.ndarray) -> Dict[str, float]:
+    """the 12 COCO numbers from precision [T,R,K,A,M] / recall [T,K,A,M] (-1 = no ground truth: left out of the means)"""
+    def ap(iou=None, area="all", max_det=100):
+        a, m = list(AREA_RNG).index(area), MAX_DETS.index(max_det)
+        p = precision[:, :, :, a, m] if iou is None else precision[np.isclose(IOU_THRS, iou)][:, :, :, a, m]
+        p = p[p > -1]
+        return float(p.mean()) if p.size else -1.0
+
+    def ar(area="all", max_det=100):
+        a, m = list(AREA_RNG).index(area), MAX_DETS.index(max_det)
+        r = recall[:, :, a, m]
+        r = r[r > -1]
+        return float(r.mean()) if r.size else -1.0
+
+    return {"bbox_mAP": ap(), "bbox_mAP_50": ap(0.5), "bbox_mAP_75": ap(0.75), "bbox_mAP_s": ap(area="small"),
+            "bbox_mAP_m": ap(area="medium"), "bbox_mAP_l": ap(area="large"), "AR@1": ar(max_det=1),
+            "AR@10": ar(max_det=10), "AR@100": ar(), "AR_s@100": ar("small"), "AR_m@100": ar("medium"),
+            "AR_l@100": ar("large")}
 
 
 class CocoBBoxEval:
@@ -136,25 +159,8 @@ class CocoBBoxEval:
                                 q[ri] = pr[pi]
                         precision[t, :, k, a, m] = q
         self.precision, self.recall = precision, recall
-
-        def ap(iou=None, area="all", max_det=100):
-            a, m = list(AREA_RNG).index(area), MAX_DETS.index(max_det)
-            p = precision[:, :, :, a, m] if iou is None else precision[np.isclose(IOU_THRS, iou)][:, :, :, a, m]
-            p = p[p > -1]
-            return float(p.mean()) if p.size else -1.0
-
-        def ar(area="all", max_det=100):
-            a, m = list(AREA_RNG).index(area), MAX_DETS.index(max_det)
-            r = recall[:, :, a, m]
-            r = r[r > -1]
-            return float(r.mean()) if r.size else -1.0
-
-        stats = {"bbox_mAP": ap(), "bbox_mAP_50": ap(0.5), "bbox_mAP_75": ap(0.75), "bbox_mAP_s": ap(area="small"),
-                 "bbox_mAP_m": ap(area="medium"), "bbox_mAP_l": ap(area="large"), "AR@1": ar(max_det=1),
-                 "AR@10": ar(max_det=10), "AR@100": ar(), "AR_s@100": ar("small"), "AR_m@100": ar("medium"),
-                 "AR_l@100": ar("large")}
-        self.stats = stats
-        return stats
+        self.stats = coco_stats(precision, recall)
+        return self.stats
 
     def classwise(self) -> Dict[str, float]:
         """AP@[.50:.95] per category (CocoMetric(classwise=True)); call evaluate() first"""
@@ -164,6 +170,97 @@ class CocoBBoxEval:
             p = p[p > -1]
             out[self.cat_names.get(cat, str(cat))] = float(p.mean()) if p.size else float("nan")
         return out
+
+
+
+class CocoBBoxEvalGPU(CocoBBoxEval):
+    """CocoBBoxEval with the matching and accumulation on the GPU (erd_coco_eval, csrc/coco_eval.hip): the same `precision` /
+    `recall` arrays bit for bit, hence the same stats, classwise() and split_map().  The ground-truth table is uploaded once;
+    detections are appended as device slots in insertion order -- from host arrays (add_predictions) or straight from
+    predict's padded tensors without a host synchronisation (add_batch).  The final means run on the host over the copied-back
+    arrays (numpy's pairwise summation is part of the result)."""
+
+    def __init__(self, gt: dict, cat_ids: Optional[Sequence[int]] = None, device=None):
+        import torch
+        super().__init__(gt, cat_ids)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self._pos: Dict[int, int] = {}
+        for i, im in enumerate(self.img_ids):
+            self._pos.setdefault(im, i)
+        I, K = len(self.img_ids), len(self.cat_ids)
+        kpos = {c: k for k, c in enumerate(self.cat_ids)}
+        pair, box, area, flag = [], [], [], []
+        for a in gt["annotations"]:                                   # annotation order is the order within a pair
+            i, k = self._pos.get(a["image_id"]), kpos.get(a["category_id"])
+            if i is None or k is None:
+                continue
+            pair.append(i * K + k)
+            box.append([float(v) for v in a["bbox"]])
+            area.append(float(a["area"]))
+            flag.append((1 if (bool(a.get("ignore", 0)) or bool(a.get("iscrowd", 0))) else 0) |
+                        (2 if bool(a.get("iscrowd", 0)) else 0))
+        pair = np.asarray(pair, dtype=np.int64)
+        order = np.argsort(pair, kind="mergesort")
+        area, flag = np.asarray(area, dtype=np.float64)[order], np.asarray(flag, dtype=np.int32)[order]
+        box = np.asarray(box, dtype=np.float64).reshape(-1, 4)[order]
+        off = np.zeros(I * K + 1, dtype=np.int32)
+        off[1:] = np.cumsum(np.bincount(pair, minlength=I * K))
+        n_gt = np.zeros((K, len(AREA_RNG)), dtype=np.int32)
+        for a, (lo, hi) in enumerate(AREA_RNG.values()):
+            keep = (flag & 1 == 0) & (lo <= area) & (area <= hi)
+            n_gt[:, a] = np.bincount(pair[order][keep] % K, minlength=K)
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
+        self._gt_dev = dict(box=up(box), area=up(area), flag=up(flag), off=up(off), n_gt=up(n_gt))
+        self._consts = dict(iou_start=up(np.minimum(IOU_THRS, 1 - 1e-10)), rec_thrs=up(REC_THRS),
+                            max_dets=up(np.asarray(MAX_DETS, dtype=np.int32)),
+                            area_rng=up(np.asarray(list(AREA_RNG.values()), dtype=np.float64)))
+        self._slots: List[tuple] = []
+
+    def positions(self, image_ids: Iterable[int]) -> List[int]:
+        """each image id's position in gt["images"] (-1: not evaluated)"""
+        return [self._pos.get(int(i), -1) for i in image_ids]
+
+    def add_predictions(self, image_id: int, bboxes_xyxy: np.ndarray, scores: np.ndarray, labels: np.ndarray) -> None:
+        """one image's detections from host arrays, converted as CocoBBoxEval.add_predictions converts them"""
+        import torch
+        b = np.asarray(bboxes_xyxy, dtype=np.float64).reshape(-1, 4)
+        if b.shape[0] == 0:
+            return
+        xywh = np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1)
+        sc = np.asarray(scores, dtype=np.float64).reshape(-1)
+        lb = np.asarray(labels).astype(int).reshape(-1)
+        K = len(self.cat_ids)
+        if lb.size and (lb.min() < -K or lb.max() >= K):
+            raise IndexError(f"label out of range for {K} categories")
+        lb = np.where(lb < 0, lb + K, lb)                              # as cat_ids[l] indexes a list
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
+        self._slots.append((up(xywh), up(sc), up(np.full(len(sc), self._pos.get(image_id, -1), dtype=np.int32)),
+                            up(lb.astype(np.int32))))
+
+    def add_batch(self, image_ids, dets, labels, num) -> None:
+        """a batch of predict's padded device outputs -- dets [N, P, 5], labels [N, P] (int64), num [N] (int32), as
+        GFLHead.predict_padded_cat returns them -- for the images `image_ids` (host ints); no host synchronisation"""
+        import torch
+        from . import kernels as K
+        pos = torch.tensor(self.positions(image_ids), dtype=torch.int32).to(self.device, non_blocking=True)
+        self._slots.append(K.coco_dets_append(dets, labels, num, pos))
+
+    def evaluate(self) -> Dict[str, float]:
+        import torch
+        from . import kernels as K
+        if self._slots:
+            box, score, img, lab = (torch.cat(x) for x in zip(*self._slots))
+        else:
+            box = torch.zeros((0, 4), dtype=torch.float64, device=self.device)
+            score = torch.zeros((0,), dtype=torch.float64, device=self.device)
+            img = lab = torch.zeros((0,), dtype=torch.int32, device=self.device)
+        self._slots = [(box, score, img, lab)]
+        c = self._consts
+        p, r = K.coco_eval(box, score, img, lab, self._gt_dev, len(self.img_ids), len(self.cat_ids), c["iou_start"],
+                           c["rec_thrs"], c["max_dets"], c["area_rng"])
+        self.precision, self.recall = p.cpu().numpy(), r.cpu().numpy()
+        self.stats = coco_stats(self.precision, self.recall)
+        return self.stats
 
 
 def split_map(ev: CocoBBoxEval, old_cat_ids: Iterable[int]) -> Dict[str, float]:

@@ -1422,6 +1422,47 @@ def tta_merge(dets: Tensor, labels: Tensor, num: Tensor, flip, ori_w, iou_thr: f
     return out_dets, out_labels, out_num
 
 
+def coco_dets_append(dets: Tensor, labels: Tensor, num: Tensor, img_index: Tensor):
+    """predict's padded outputs dets [N, P, 5], labels [N, P] (int64), num [N] (int32) and each image's position in
+    gt["images"] (img_index [N] int32, -1: not evaluated) as COCO-evaluator detection slots, (image, row) order: box [N*P, 4]
+    fp64 xywh, score [N*P] fp64, img / label [N*P] int32 (-1 on padding rows).  No host synchronisation."""
+    _require_gpu(dets, labels, num, img_index)
+    N, P, _ = dets.shape
+    assert dets.dtype == torch.float32 and labels.dtype == torch.int64 and num.dtype == torch.int32
+    assert img_index.dtype == torch.int32 and labels.shape == (N, P) and num.shape == (N,) and img_index.shape == (N,)
+    dets, labels, num, img_index = dets.contiguous(), labels.contiguous(), num.contiguous(), img_index.contiguous()
+    dev = dets.device
+    box = torch.empty((N * P, 4), dtype=torch.float64, device=dev)
+    score = torch.empty((N * P,), dtype=torch.float64, device=dev)
+    img = torch.empty((N * P,), dtype=torch.int32, device=dev)
+    label = torch.empty((N * P,), dtype=torch.int32, device=dev)
+    call("erd_coco_dets_append", _p(dets), _p(labels), _p(num), _p(img_index), N, P, _p(box), _p(score), _p(img), _p(label),
+         _stream())
+    return box, score, img, label
+
+
+def coco_eval(dt_box: Tensor, dt_score: Tensor, dt_img: Tensor, dt_label: Tensor, gt: Dict[str, Tensor], I: int, K: int,
+              iou_start: Tensor, rec_thrs: Tensor, max_dets: Tensor, area_rng: Tensor):
+    """COCO bbox precision [10, 101, K, 4, 3] / recall [10, K, 4, 3] (fp64, on the device) of detection slots (erd_coco_eval).
+    gt: the evaluator's device table -- box [G, 4], area [G], flag [G] (int32), off [I*K + 1] (int32), n_gt [K, 4] (int32)."""
+    _require_gpu(dt_box, dt_score, dt_img, dt_label, gt["off"], gt["n_gt"])
+    D = int(dt_score.shape[0])
+    assert dt_box.shape == (D, 4) and dt_box.dtype == torch.float64 and dt_score.dtype == torch.float64
+    assert dt_img.dtype == torch.int32 and dt_label.dtype == torch.int32 and dt_img.shape == (D,) and dt_label.shape == (D,)
+    G = int(gt["area"].shape[0])
+    assert gt["off"].shape == (I * K + 1,) and gt["n_gt"].shape == (K, 4) and gt["box"].shape == (G, 4)
+    assert len(iou_start) == 10 and len(rec_thrs) == 101 and len(max_dets) == 3 and area_rng.shape == (4, 2)
+    dev = dt_score.device
+    precision = torch.empty((10, 101, K, 4, 3), dtype=torch.float64, device=dev)
+    recall = torch.empty((10, K, 4, 3), dtype=torch.float64, device=dev)
+    nbytes = int(_lib.load().erd_coco_eval_ws_bytes(D, I * K, K, G))
+    ws = workspace("coco_eval", nbytes, dev)
+    call("erd_coco_eval", _p(dt_box), _p(dt_score), _p(dt_img), _p(dt_label), D, _p(gt["box"]), _p(gt["area"]), _p(gt["flag"]),
+         _p(gt["off"]), I, K, G, _p(gt["n_gt"]), _p(area_rng), _p(iou_start), _p(rec_thrs), _p(max_dets), _p(precision),
+         _p(recall), _p(ws), C.c_size_t(nbytes), _stream())
+    return precision, recall
+
+
 def kd_kl(s_bbox, t_bbox, s_cls, keep, c_old, T):
     N, A, c_s = s_cls.shape
     sums = torch.empty((N,), dtype=torch.float64, device=s_cls.device)

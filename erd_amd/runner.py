@@ -23,6 +23,7 @@ from .config import Config
 from .engine import ERDTrainer
 from .registry import MODELS
 from .structures import DetDataSample, InstanceData
+from .validation import val_due
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -206,7 +207,10 @@ def _with_next(it, prepare):
 
 
 class Runner:
-    def __init__(self, cfg: Config, data=None, device: Optional[torch.device] = None, log: Callable[[str], None] = print):
+    def __init__(self, cfg: Config, data=None, device: Optional[torch.device] = None, log: Callable[[str], None] = print,
+                 val_data: Optional[dict] = None):
+        """data: the training batches; val_data: keys that replace the config's `val_dataloader.dataset` ones (ann_file,
+        data_root, data_prefix, ...)"""
         self.cfg = cfg
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         self.world = dist.get_world_size() if dist.is_initialized() else 1
@@ -244,6 +248,14 @@ class Runner:
         self.data = data
         self.epoch = 0
         self.history: List[Dict[str, float]] = []
+        # validation after each epoch (mmengine ValLoop): train_cfg.val_begin / val_interval, val_dataloader, val_evaluator
+        from .validation import CocoValidator, skip_reason
+        self.val_begin = int(cfg.train_cfg.get("val_begin", 1))
+        self.val_interval = int(cfg.train_cfg.get("val_interval", 1))
+        why = skip_reason(cfg, val_data)
+        self.validator = None if why else CocoValidator.from_cfg(cfg, val_data, device=self.device)
+        if why:
+            self.log(f"validation skipped: {why}")
         load_from, resume = cfg.get("load_from"), bool(cfg.get("resume", False))
         if resume and not load_from:
             last = os.path.join(self.work_dir, "last_checkpoint")
@@ -303,10 +315,31 @@ class Runner:
                 with open(os.path.join(self.work_dir, "last_checkpoint"), "w") as f:
                     f.write(path)
                 self.log(f"saved {path}")
+            if self.validator is not None and val_due(self.epoch, self.max_epochs, self.val_begin, self.val_interval):
+                self.validate()
         self.trainer.flush()
+        self._write_scalars()
+        return self.history
+
+    def validate(self) -> Dict[str, float]:
+        """one validation pass of the live student on the weights after the epoch's last update (those epoch_{e}.pth holds):
+        the deferred update is applied and every stream drained first; the pass reads the trainer's state and changes none of it"""
+        if self.validator is None:
+            raise RuntimeError("this runner has no validation (val_cfg / val_dataloader / val_evaluator or its file is missing)")
+        self.trainer.flush()
+        torch.cuda.synchronize(self.device)                   # teacher look-ahead stream, per-bucket update stream
+        t0 = time.perf_counter()
+        stats = self.validator.run(self.model)
+        torch.cuda.synchronize(self.device)
+        for line in self.validator.format(self.epoch, stats):
+            self.log(line)
+        rec = dict(mode="val", epoch=self.epoch, time=time.perf_counter() - t0, **{f"coco/{k}": v for k, v in stats.items()})
+        self.history.append(rec)
+        return stats
+
+    def _write_scalars(self) -> None:
         if self.rank == 0:
             os.makedirs(self.work_dir, exist_ok=True)
             with open(os.path.join(self.work_dir, "scalars.json"), "w") as f:
                 for rec in self.history:
                     f.write(json.dumps(rec) + "\n")
-        return self.history

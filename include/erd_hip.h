@@ -444,6 +444,24 @@ int erd_tta_merge(const float* dets, const int64_t* labels, const int32_t* num, 
                   const int32_t* flip, const float* ori_w, float iou_thr, int max_per_img, float* out_dets,
                   int64_t* out_labels, int32_t* out_num, void* ws, size_t ws_bytes, erd_stream_t stream);
 
+/* ---- COCO bounding-box evaluation on the device (erd_amd/evaluation.py CocoBBoxEvalGPU; the host restatement CocoBBoxEval is the
+ * contract: the same precision / recall arrays, bit for bit) ----------------------------------------------------------------------
+ * erd_coco_dets_append: predict's padded outputs -- dets [N][P][5] (x1,y1,x2,y2,score), labels [N][P] int64, num [N] -- plus each
+ * image's position in gt["images"] (img_index [N], -1: not evaluated) into detection slots, in (image, row) order: box [N*P][4] =
+ * (x1, y1, x2 - x1, y2 - y1) in fp64, score [N*P] fp64, img / label [N*P] (-1 for the padding rows j >= num[n]).
+ * erd_coco_eval: slots [D] in insertion order (ties of equal scores keep it); ground truth as CSR over pairs p = image * K +
+ * category: rows gt_off[p] .. gt_off[p+1]-1 in annotation order, box [ngt][4] xywh, area [ngt] (the annotation's `area`),
+ * flag [ngt] (bit 0: ignore or iscrowd, bit 1: iscrowd); n_gt [K][4] the non-ignored count per area range; area_rng [4][2],
+ * iou_start [10] = min(iouThr, 1 - 1e-10), rec_thrs [101], max_dets [3] (ascending, the last 100).
+ * precision [10][101][K][4][3], recall [10][K][4][3] fp64.  ws: erd_coco_eval_ws_bytes(D, I*K, K, ngt) bytes. */
+int erd_coco_dets_append(const float* dets, const int64_t* labels, const int32_t* num, const int32_t* img_index, int N, int P,
+                         double* box, double* score, int32_t* img, int32_t* label, erd_stream_t stream);
+size_t erd_coco_eval_ws_bytes(int64_t D, int npairs, int K, int64_t ngt);
+int erd_coco_eval(const double* dt_box, const double* dt_score, const int32_t* dt_img, const int32_t* dt_label, int64_t D,
+                  const double* gt_box, const double* gt_area, const int32_t* gt_flag, const int32_t* gt_off, int I, int K,
+                  int64_t ngt, const int32_t* n_gt, const double* area_rng, const double* iou_start, const double* rec_thrs,
+                  const int32_t* max_dets, double* precision, double* recall, void* ws, size_t ws_bytes, erd_stream_t stream);
+
 /* ---- stand-alone leaf operators: what the registered loss / coder / assigner MODULES run when a caller invokes them
  * directly (the training step itself uses the fused erd_gfl_losses_* / erd_kd_kl* kernels above).  Row-parallel; every
  * loss comes as `rows` (the reference's reduction='none' value, after the per-row sum / mean the reference applies) plus

@@ -11,7 +11,10 @@ erd_amd.evaluation.CocoBBoxEval (COCOeval restated, unpinned).
 --tta (reference tools/test.py:93-120): the detector runs inside DetTTAModel on every view the config's tta_pipeline
 makes (scales x horizontal flips; without tta_model / tta_pipeline the flip-only defaults at the test Resize scale) and
 the views' detections are merged per image on the GPU (erd_tta_merge).  `--cfg-options test_evaluator.classwise=True`
-prints the class-wise AP table as CocoMetric(classwise=True) does."""
+prints the class-wise AP table as CocoMetric(classwise=True) does.
+
+--gpu-eval: the device evaluator (CocoBBoxEvalGPU, bit-equal arrays); --launcher pytorch (tools/dist_test.sh): each rank predicts
+its DefaultSampler(shuffle=False) shard, rank 0 evaluates the gathered detections on its GPU and prints."""
 import argparse
 import json
 import os
@@ -33,6 +36,10 @@ def main(argv=None):
     ap.add_argument("--max-images", type=int, default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--tta", action="store_true", help="test-time augmentation (tta_model / tta_pipeline of the config)")
+    ap.add_argument("--gpu-eval", action="store_true", help="COCO evaluation on the GPU (CocoBBoxEvalGPU: the same numbers)")
+    ap.add_argument("--launcher", choices=["none", "pytorch"], default="none",
+                    help="pytorch: sharded over the ranks of torch.distributed.run (DefaultSampler(shuffle=False)), device evaluation")
+    ap.add_argument("--local_rank", "--local-rank", type=int, default=0)
     a = ap.parse_args(argv)
 
     import torch
@@ -42,6 +49,12 @@ def main(argv=None):
     from erd_amd.evaluation import CocoBBoxEval, split_map
     from erd_amd.runner import load_checkpoint
 
+    if a.launcher == "pytorch":
+        import torch.distributed as dist
+        from erd_amd.dist_utils import backend_name, device_index
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        torch.cuda.set_device(device_index(int(os.environ.get("LOCAL_RANK", a.local_rank))))
+        dist.init_process_group(backend_name())      # 'nccl' (= RCCL) unless ERD_DIST_BACKEND=gloo
     cfg = Config.fromfile(a.config)
     cfg.merge_from_dict(parse_cfg_options(a.cfg_options))
     if cfg.model.get("latest_model_flag") is not None:
@@ -59,6 +72,9 @@ def main(argv=None):
     detector.load_state_dict({**{k: v for k, v in own.items() if k not in sd}, **sd}, strict=True)
 
     dcfg = cfg.test_dataloader.dataset
+    n_old = a.old_classes if a.old_classes is not None else (cfg.model.get("ori_setting") or {}).get("ori_num_classes")
+    if a.gpu_eval or a.launcher == "pytorch":
+        return _device_eval(a, cfg, detector, dcfg, n_old)
     root = dcfg.get("data_root", "")
     gt = json.load(open(os.path.join(root, dcfg["ann_file"])))
     ann = CocoAnnotations(gt, (dcfg.get("metainfo") or {}).get("classes"),
@@ -85,7 +101,6 @@ def main(argv=None):
             for (x1, y1, x2, y2), s, l in zip(bb.tolist(), sc.tolist(), lb.tolist()):
                 results.append(dict(image_id=img_id, category_id=ann.cat_ids[l], bbox=[x1, y1, x2 - x1, y2 - y1], score=s))
     stats = ev.evaluate()
-    n_old = a.old_classes if a.old_classes is not None else (cfg.model.get("ori_setting") or {}).get("ori_num_classes")
     if n_old:
         stats.update(split_map(ev, ann.cat_ids[:n_old]))
     for k, v in stats.items():
@@ -96,6 +111,32 @@ def main(argv=None):
             print(f"{str(name):24s} {v:.4f}")
     if a.out:
         json.dump(dict(stats=stats, classwise=ev.classwise(), results=results), open(a.out, "w"))
+    return stats
+
+
+def _device_eval(a, cfg, detector, dcfg, n_old):
+    """--gpu-eval / --launcher pytorch: predict's padded outputs straight into the device evaluator; at world > 1 each rank
+    predicts its shard and rank 0 evaluates the gathered detections (erd_amd.validation.CocoValidator)"""
+    import torch.distributed as dist
+    from erd_amd.validation import CocoValidator
+    if a.tta:
+        raise NotImplementedError("--tta runs with the host evaluator in one process")
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    val = CocoValidator(dcfg, batch_size=a.batch_size, num_workers=int(cfg.test_dataloader.get("num_workers", 0)),
+                        classwise=bool((cfg.get("test_evaluator") or {}).get("classwise", False)), old_classes=n_old)
+    stats = val.run(detector, max_images=a.max_images)
+    if rank == 0:
+        for k, v in stats.items():
+            print(f"{k:12s} {v:.4f}")
+        if val.classwise:
+            print(f"{'category':24s} mAP")
+            for name, v in val.last["classwise"].items():
+                print(f"{str(name):24s} {v:.4f}")
+        if a.out:
+            json.dump(dict(stats=stats, classwise=val.last["classwise"]), open(a.out, "w"))
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
     return stats
 
 
