@@ -92,6 +92,7 @@ _SIGNATURES = {
     "erd_conv_wgrad": [C.POINTER(WgradDesc), P],
     "erd_wgrad_row3_slices": [C.POINTER(WgradDesc)],
     "erd_wgrad_reduce": [P, i32, i32, i32, P, P, P, i32, P, P],
+    "erd_wgrad_reduce_rows": [P, i32, i32, i32, i32, P, i32, P],
     "erd_weight_transpose": [P, P, P, i32, i32, i32, i32, P],
     "erd_weight_transpose_bf16": [P, P, P, i32, i32, i32, i32, P],
     "erd_stem_conv7x7_bn_relu": [P, P, P, P, P, i32, i32, i32, P],
@@ -108,6 +109,7 @@ _SIGNATURES = {
     "erd_upsample2x_add": [P, P, i32, i32, i32, i32, i32, i32, i64, i64, i32, P],
     "erd_upsample2x_add_bwd": [P, P, i32, i32, i32, i32, i32, i32, i64, i64, i32, P],
     "erd_colsum": [P, i64, i32, P, i32, i32, P],
+    "erd_pad_channels": [P, P, i64, i32, i32, P],
     "erd_level_scale": [P, P, P, i32, i64, i32, C.POINTER(Levels), P],
     "erd_level_scale_bwd": [P, P, P, P, P, i32, i64, i32, C.POINTER(Levels), P],
     "erd_sgd_momentum": [P, P, P, i64, f32, f32, f32, f32, i32, P],

@@ -2278,6 +2278,15 @@ extern "C" int erd_wgrad_reduce(const float* part, int nsplit, int Cout, int K, 
     return erd::check_launch("wgrad_reduce");
 }
 
+extern "C" int erd_wgrad_reduce_rows(const float* part, int nsplit, int Cout_slab, int Cout, int K, float* dW,
+                                     int accumulate, erd_stream_t stream) {
+    ERD_REQUIRE(part && dW && nsplit >= 1 && K % 4 == 0 && Cout >= 1 && Cout <= Cout_slab, "wgrad_reduce_rows: bad args");
+    // the kernel's block co reduces row co of each [Cout_slab][K] slab: a grid of Cout blocks leaves the padding rows out
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(Cout, (K + 1023) / 1024), dim3(256), 0, (hipStream_t)stream, part,
+                       nsplit, Cout_slab, K, nullptr, nullptr, dW, accumulate & 1, nullptr);
+    return erd::check_launch("wgrad_reduce_rows");
+}
+
 extern "C" int erd_weight_transpose(const float* w, const float* rowscale, float* dst, int Cout, int ntaps,
                                     int Cin, int flip, erd_stream_t stream) {
     ERD_REQUIRE(w && dst && Cout > 0 && Cin > 0 && ntaps > 0, "weight_transpose: bad args");

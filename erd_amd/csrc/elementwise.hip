@@ -626,6 +626,18 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, in
     }
 }
 
+// dst[r][c] = c < C ? src[r][c] : 0 over [rows][Cp]: a channel count that is not a multiple of 4 brought to the GEMM kernels'
+// 4-channel groups (the gfl_cls backward of a 70-class head runs at 80 channels)
+__global__ __launch_bounds__(256) void pad_channels_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                           int64_t rows, int C, int Cp) {
+    const int64_t n = rows * Cp;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / Cp;
+        const int c = (int)(i - r * Cp);
+        dst[i] = c < C ? src[r * C + c] : 0.f;
+    }
+}
+
 // y = x * alpha[level]  over [N][A][C] (gfl_head.py:229 `scale(self.gfl_reg(reg_feat))`, one Scale per level)
 __global__ __launch_bounds__(256) void level_scale_kernel(const float* __restrict__ x, const float* __restrict__ alphas,
                                                           float* __restrict__ y, int64_t A, int C, erd_levels lv,
@@ -981,6 +993,14 @@ extern "C" int erd_colsum(const void* x, int64_t rows, int C, float* out, int ac
     ERD_MAP(map_type, hipLaunchKernelGGL(colsum_kernel<T>, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, st,
                                          (const T*)x, rows, C, out, rpb));
     return erd::check_launch("colsum");
+}
+
+extern "C" int erd_pad_channels(const float* src, float* dst, int64_t rows, int C, int Cp, erd_stream_t stream) {
+    ERD_REQUIRE(src && dst && rows >= 0 && C > 0 && Cp >= C, "pad_channels: bad args");
+    if (rows == 0) return 0;
+    const int64_t blocks = std::min<int64_t>((rows * Cp + 255) / 256, 8192);
+    hipLaunchKernelGGL(pad_channels_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, dst, rows, C, Cp);
+    return erd::check_launch("pad_channels");
 }
 
 extern "C" int erd_level_scale(const float* x, const float* alphas, float* y, int N, int64_t A, int C,

@@ -374,6 +374,30 @@ __device__ __forceinline__ int level_of(const Levels5& lv, int64_t a) {
 // with coalesced float4 loads, and thread t (<64) finishes anchor t.  Positives (rare) do the box work.
 constexpr int GL_ROWS = 64;
 
+// The 64 rows of a block are ONE contiguous run of nrows * C floats, which starts 16-byte aligned only when
+// N * A * C and C are multiples of 4.  The run is staged at LDS offset `off` = (its global float index mod 4),
+// so that a global float4 and its LDS float4 are both naturally aligned: scalar head up to the first aligned
+// address, float4 body, scalar tail.  At C % 4 == 0 on an aligned map, off = head = tail = 0.
+__device__ __forceinline__ int gl_lds_off(const float* g) { return (int)((reinterpret_cast<uintptr_t>(g) >> 2) & 3); }
+
+// dst[i] = src[i], i < len; dst and src share their address mod 16 (the float4 body is aligned on both sides)
+__device__ __forceinline__ void gl_copy_run(float* dst, const float* src, int len) {
+    const int head = min(len, (4 - gl_lds_off(src)) & 3);
+    const int n4 = (len - head) >> 2;
+    const float4* s4 = reinterpret_cast<const float4*>(src + head);
+    float4* d4 = reinterpret_cast<float4*>(dst + head);
+    for (int i = threadIdx.x; i < n4; i += 256) d4[i] = s4[i];
+    const int t0 = head + 4 * n4;
+    if ((int)threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
+    if ((int)threadIdx.x < len - t0) dst[t0 + threadIdx.x] = src[t0 + threadIdx.x];
+}
+
+// LDS bytes of one block: 3 spare floats whenever a run may start off a 16-byte boundary
+inline size_t gl_lds_bytes(const float* cls, int c_all) {
+    const bool aligned = (reinterpret_cast<uintptr_t>(cls) & 15) == 0 && (c_all & 3) == 0;
+    return (GL_ROWS * (size_t)c_all + (aligned ? 0 : 3)) * sizeof(float);
+}
+
 template <bool BWD>
 __global__ __launch_bounds__(256) void gfl_losses_kernel(const float* __restrict__ cls, const float* __restrict__ bbox,
                                                           const float4* __restrict__ anchors,
@@ -384,13 +408,14 @@ __global__ __launch_bounds__(256) void gfl_losses_kernel(const float* __restrict
                                                           float* __restrict__ wt_ws, double* __restrict__ out_sums,
                                                           const float* __restrict__ coef, float* __restrict__ dcls,
                                                           float* __restrict__ dbbox) {
-    extern __shared__ float sm[];  // [GL_ROWS][c_all] logits (then grads)
+    extern __shared__ __attribute__((aligned(16))) float sm_base[];  // [off + GL_ROWS * c_all] logits (then grads)
     const int n = blockIdx.y;
     const int64_t a0 = (int64_t)blockIdx.x * GL_ROWS;
     const int nrows = (int)imin64(GL_ROWS, A - a0);
-    const int C = c_all, C4 = C >> 2, cn = c_all - c_old;
-    const float4* src = reinterpret_cast<const float4*>(cls + ((int64_t)n * A + a0) * C);
-    for (int i = threadIdx.x; i < nrows * C4; i += 256) reinterpret_cast<float4*>(sm)[i] = src[i];
+    const int C = c_all, cn = c_all - c_old;
+    const float* src = cls + ((int64_t)n * A + a0) * C;
+    float* sm = sm_base + gl_lds_off(src);
+    gl_copy_run(sm, src, nrows * C);
     __syncthreads();
 
     // 4 threads per anchor row: thread q of row r handles new channels q, q+4, ...
@@ -489,8 +514,12 @@ __global__ __launch_bounds__(256) void gfl_losses_kernel(const float* __restrict
     }
     if (BWD) {
         __syncthreads();
-        float4* dst = reinterpret_cast<float4*>(dcls + ((int64_t)n * A + a0) * C);
-        for (int i = threadIdx.x; i < nrows * C4; i += 256) dst[i] = reinterpret_cast<float4*>(sm)[i];
+        float* dst = dcls + ((int64_t)n * A + a0) * C;
+        if (gl_lds_off(dst) == gl_lds_off(src)) {
+            gl_copy_run(dst, sm, nrows * C);
+        } else {      // dcls and cls differ in alignment: scalar write-back
+            for (int i = threadIdx.x; i < nrows * C; i += 256) dst[i] = sm[i];
+        }
         return;
     }
     // ---- forward reductions: per level {qfl, giou*w, dfl*w, w}: LDS partials, one global atomic per block ----
@@ -863,12 +892,12 @@ extern "C" int erd_gfl_losses_fwd(const float* cls, const float* bbox, const flo
                                   float* score_ws, float* wt_ws, double* out_sums, erd_stream_t stream) {
     ERD_REQUIRE(cls && bbox && anchors && labels && label_weights && bbox_targets && lvl_off && strides && score_ws &&
                     wt_ws && out_sums, "gfl_losses_fwd: null");
-    ERD_REQUIRE(c_all % 4 == 0 && c_old >= 0 && c_old < c_all && nlvl <= ERD_MAX_SEG, "gfl_losses_fwd: channels");
+    ERD_REQUIRE(c_all >= 1 && c_old >= 0 && c_old < c_all && nlvl <= ERD_MAX_SEG, "gfl_losses_fwd: channels");
     hipStream_t st = (hipStream_t)stream;
     const Levels5 lv = make_levels(lvl_off, strides, nlvl, nullptr, nullptr);
     ERD_ZERO_ASYNC(out_sums, sizeof(double) * 4 * nlvl, st);
     hipLaunchKernelGGL(gfl_losses_kernel<false>, dim3((unsigned)((A + GL_ROWS - 1) / GL_ROWS), N), dim3(256),
-                       GL_ROWS * c_all * sizeof(float), st, cls, bbox, reinterpret_cast<const float4*>(anchors), labels,
+                       gl_lds_bytes(cls, c_all), st, cls, bbox, reinterpret_cast<const float4*>(anchors), labels,
                        label_weights, reinterpret_cast<const float4*>(bbox_targets), lv, A, c_old, c_all, score_ws,
                        wt_ws, out_sums, nullptr, nullptr, nullptr);
     return erd::check_launch("gfl_losses_fwd");
@@ -881,9 +910,10 @@ extern "C" int erd_gfl_losses_bwd(const float* cls, const float* bbox, const flo
                                   float* dbbox, erd_stream_t stream) {
     ERD_REQUIRE(cls && bbox && anchors && labels && label_weights && bbox_targets && lvl_off && strides && score_ws &&
                     coef && dcls && dbbox, "gfl_losses_bwd: null");
+    ERD_REQUIRE(c_all >= 1 && c_old >= 0 && c_old < c_all && nlvl <= ERD_MAX_SEG, "gfl_losses_bwd: channels");
     const Levels5 lv = make_levels(lvl_off, strides, nlvl, nullptr, nullptr);
     hipLaunchKernelGGL(gfl_losses_kernel<true>, dim3((unsigned)((A + GL_ROWS - 1) / GL_ROWS), N), dim3(256),
-                       GL_ROWS * c_all * sizeof(float), (hipStream_t)stream, cls, bbox,
+                       gl_lds_bytes(cls, c_all), (hipStream_t)stream, cls, bbox,
                        reinterpret_cast<const float4*>(anchors), labels, label_weights,
                        reinterpret_cast<const float4*>(bbox_targets), lv, A, c_old, c_all,
                        const_cast<float*>(score_ws), const_cast<float*>(wt_ws), nullptr, coef, dcls, dbbox);

@@ -776,6 +776,8 @@ class HeadConvBias(Function):
         sizes = ctx.sizes
         dy = dy.contiguous()
         wk = ohwi(w)
+        if wk.shape[0] % 4:
+            return HeadConvBias._backward_padded(ctx, x_cat, w, wk, dy, sizes)
         dW = db = dx = None
         xv, dv = K.level_views(x_cat, sizes), K.level_views(dy, sizes)
         if ctx.needs_input_grad[1]:
@@ -785,6 +787,35 @@ class HeadConvBias(Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x_cat)
             K.conv_dgrad(dv, K.weight_transpose(wk), K.level_views(dx, sizes), 3, 1, 1)
+        return dx, dW, db, None
+
+    @staticmethod
+    def _backward_padded(ctx, x_cat, w, wk, dy, sizes):
+        """Cout % 4 != 0 (a 70- or 50-class gfl_cls): both gradients contract over Cout, which the GEMM kernels take in
+        4-channel groups.  They run at Cp = round_up(Cout, 16) -- the 80-class head's launches for 70 classes -- on
+        zero-padded copies of dy and of the weight; the padding channels contribute exact zeros.  The weight gradient
+        reduces only rows [0, Cout) of the [S, Cp, 9 * Cin] partial slabs; the bias gradient is the column sum over Cout."""
+        Cout = wk.shape[0]
+        Cp = (Cout + 15) // 16 * 16
+        dyp = K.pad_channels(dy, Cp)
+        dvp = K.level_views(dyp, sizes)
+        dW = db = dx = None
+        if ctx.needs_input_grad[1]:
+            part, S = K.conv_wgrad_partials(K.level_views(x_cat, sizes), dvp, 3, 1, 1)
+            sink = _sink(w)
+            if sink is not None:
+                K.wgrad_reduce_rows(part, S, Cp, ohwi(sink), True)
+                _sunk(w)
+            else:
+                dWk = torch.empty_like(wk)
+                K.wgrad_reduce_rows(part, S, Cp, dWk, False)
+                dW = _to_oihw(dWk)
+        if ctx.needs_input_grad[2]:
+            db = _bias_grad(ctx.bias_param, dy)
+        if ctx.needs_input_grad[0]:
+            wp = K.pad_channels(wk.reshape(1, -1), Cp * wk[0].numel()).view(Cp, *wk.shape[1:])
+            dx = torch.empty_like(x_cat)
+            K.conv_dgrad(dvp, K.weight_transpose(wp), K.level_views(dx, sizes), 3, 1, 1)
         return dx, dW, db, None
 
 

@@ -1026,6 +1026,23 @@ def _wgrad_desc(xs, dzs, k, stride, pad, xoff, zoff):
     return d, S, flop, nbytes, f"px{npix} {Cin}->{Cout} k{k}s{stride} S{S}", Cout, Cin, bool(row3)
 
 
+def wgrad_reduce_rows(part: Tensor, S: int, Cout_slab: int, dW: Tensor, accumulate: bool) -> None:
+    """dW (+)= rows [0, dW.shape[0]) of the [S, Cout_slab, K] partial slabs (a convolution run at a zero-padded Cout)"""
+    Cout = dW.shape[0]
+    call("erd_wgrad_reduce_rows", _p(part), S, Cout_slab, Cout, dW.numel() // Cout, _p(dW), 1 if accumulate else 0,
+         _stream())
+
+
+def pad_channels(src: Tensor, Cp: int) -> Tensor:
+    """fp32 [..., C] -> [..., Cp] with zeros in channels [C, Cp)"""
+    _require_gpu(src)
+    assert src.dtype == torch.float32 and src.is_contiguous()
+    C = src.shape[-1]
+    out = torch.empty((*src.shape[:-1], Cp), dtype=torch.float32, device=src.device)
+    call("erd_pad_channels", _p(src), _p(out), src.numel() // C, C, Cp, _stream())
+    return out
+
+
 def wgrad_reduce(part: Tensor, S: int, w: Tensor, rowscale: Optional[Tensor], dW: Tensor, accumulate: bool,
                  rowdot: Optional[Tensor], rowdot_zeroed: bool = False) -> None:
     """rowdot_zeroed: the caller took rowdot from the step's zero arena (zeros_f32): no memset launch"""

@@ -1034,12 +1034,20 @@ def load_state_dict_strict(module: nn.Module, state_dict: Dict[str, Tensor]) -> 
     module.load_state_dict(state_dict, strict=True)
 
 
-def load_checkpoint(model: nn.Module, filename: str, strict: bool = True) -> dict:
+def _without_teacher(state_dict: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """a GFLIncrementERD checkpoint minus its frozen teacher copy (`ori_model.*`, `module.ori_model.*`)"""
+    return OrderedDict((k, v) for k, v in state_dict.items()
+                       if not (k[7:] if k.startswith("module.") else k).startswith("ori_model."))
+
+
+def load_checkpoint(model: nn.Module, filename: str, strict: bool = True, drop_teacher: bool = False) -> dict:
+    """drop_teacher: the file is an earlier ERD phase's checkpoint -- its `ori_model.*` copy is that phase's teacher and is
+    not loaded; every other key stays strict"""
     ckpt = torch.load(filename, map_location="cpu", weights_only=False)
     sd = ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt
     if not isinstance(sd, dict):
         raise RuntimeError(f"No state_dict found in checkpoint file {filename}")
-    load_state_dict_strict(model, sd)
+    load_state_dict_strict(model, _without_teacher(sd) if drop_teacher else sd)
     return ckpt
 
 
@@ -1058,8 +1066,9 @@ class GFLIncrementERD(GFL):
             self.load_base_detector(ori_setting)
             self._is_init = True
 
-    def _load_checkpoint_for_new_model(self, checkpoint_file: str, strict: bool = True) -> None:
-        """:67-93 -- warm start: teacher checkpoint with gfl_cls widened by the student's fresh new-class rows."""
+    def _load_checkpoint_for_new_model(self, checkpoint_file: str, strict: bool = True, drop_teacher: bool = False) -> None:
+        """:67-93 -- warm start: teacher checkpoint with gfl_cls widened by the student's fresh new-class rows.
+        drop_teacher: the file is an earlier ERD phase's (its `ori_model.*` copy is not part of the student)."""
         checkpoint = torch.load(checkpoint_file, map_location="cpu", weights_only=False)
         if isinstance(checkpoint, OrderedDict):
             state_dict = checkpoint
@@ -1069,7 +1078,7 @@ class GFLIncrementERD(GFL):
             raise RuntimeError("No state_dict found in checkpoint file {}".format(checkpoint_file))
         if list(state_dict.keys())[0].startswith("module."):
             state_dict = {k[7:]: v for k, v in checkpoint["state_dict"].items()}
-        state_dict = dict(state_dict)
+        state_dict = dict(_without_teacher(state_dict)) if drop_teacher else dict(state_dict)
         w, b = self.bbox_head.gfl_cls.weight.detach().cpu(), self.bbox_head.gfl_cls.bias.detach().cpu()
         state_dict["bbox_head.gfl_cls.weight"] = torch.cat(
             (state_dict["bbox_head.gfl_cls.weight"], w[self.ori_num_classes:, ...]), dim=0)
@@ -1082,12 +1091,18 @@ class GFLIncrementERD(GFL):
         assert os.path.isfile(ori_setting["ori_checkpoint_file"]), "{} is not a valid file".format(
             ori_setting["ori_checkpoint_file"])
         ori_cfg = Config.fromfile(ori_setting["ori_config_file"])
-        if "latest_model_flag" in ori_cfg.model:
+        # a chained phase: the teacher is the previous phase's GFLIncrementERD, built without ITS teacher; the previous
+        # phase's checkpoint carries that teacher as `ori_model.*`, which neither load takes
+        chained = ori_cfg.model.get("type") == "GFLIncrementERD"
+        if "latest_model_flag" in ori_cfg.model or chained:
             ori_cfg.model.latest_model_flag = False
         ori_model = MODELS.build(ori_cfg.model)
-        load_checkpoint(ori_model, ori_setting["ori_checkpoint_file"], strict=True)
+        if ori_setting["ori_num_classes"] != ori_model.bbox_head.num_classes:
+            raise ValueError(f"ori_setting.ori_num_classes = {ori_setting['ori_num_classes']} but the teacher "
+                             f"{ori_setting['ori_config_file']} has a {ori_model.bbox_head.num_classes}-class head")
+        load_checkpoint(ori_model, ori_setting["ori_checkpoint_file"], strict=True, drop_teacher=chained)
         self.ori_num_classes = ori_setting["ori_num_classes"]
-        self._load_checkpoint_for_new_model(ori_setting["ori_checkpoint_file"])
+        self._load_checkpoint_for_new_model(ori_setting["ori_checkpoint_file"], drop_teacher=chained)
         print("======> load base checkpoint for new model from {}".format(ori_setting["ori_checkpoint_file"]), file=sys.stderr)
         self.attach_teacher(ori_model, self.ori_num_classes)
 

@@ -230,6 +230,11 @@ int erd_wgrad_row3_slices(const erd_wgrad_desc* d);
 int erd_wgrad_reduce(const float* part, int nsplit, int Cout, int K, const float* w,
                      const float* rowscale, float* dW, int accumulate, float* rowdot,
                      erd_stream_t stream);
+/* dW[co][:] (+)= sum_s part[s][co][:] for co < Cout of [nsplit][Cout_slab][K] slabs (Cout <= Cout_slab): the weight
+ * gradient of a convolution run at a zero-padded output width (gfl_cls of a head whose class count is not a multiple
+ * of 4, gfl_head.py:224-229).  accumulate: bit 0 = add into dW. */
+int erd_wgrad_reduce_rows(const float* part, int nsplit, int Cout_slab, int Cout, int K, float* dW, int accumulate,
+                          erd_stream_t stream);
 
 /* dst[ci][t'][co] = rowscale[co] * w[co][t][ci]  (t' = flip ? ntaps-1-t : t): weights of the
  * input-gradient convolution. */
@@ -337,6 +342,9 @@ int erd_upsample2x_add_bwd(const void* dfine, void* dcoarse, int N, int H, int W
 
 /* ---- small dense helpers -------------------------------------------------------------------- */
 int erd_colsum(const void* x, int64_t rows, int C, float* out, int accumulate, int map_type /* of x */, erd_stream_t stream);
+/* dst[r][c] = c < C ? src[r][c] : 0 over fp32 [rows][Cp], Cp >= C: the gradient of a head output with C % 4 != 0
+ * classes (and its weight, rows = 1) widened for the padded gfl_cls backward (gfl_head.py:224-229) */
+int erd_pad_channels(const float* src, float* dst, int64_t rows, int C, int Cp, erd_stream_t stream);
 /* y[n][a][:] = x[n][a][:] * alphas[level(a)] (gfl_head.py:229, one learnable Scale per level) and adjoint */
 int erd_level_scale(const float* x, const float* alphas, float* y, int N, int64_t A, int C,
                     const erd_levels* lv, erd_stream_t stream);
