@@ -51,6 +51,7 @@ __device__ __forceinline__ float4 buf_load16_s(__amdgpu_buffer_rsrc_t r, unsigne
 
 constexpr int KS = 16;                        // input channels per K slice
 constexpr int BN = 64;                        // output channels per workgroup item
+constexpr int BNP = 128;                      // ... of wino_x3p_kernel
 constexpr int RCS = 6;                        // LDS chunks per raw pixel: 4 data + 2 pad -> the strided 4x4-patch reads of the
                                               // transform are bank-conflict free (4 would be 8-way)
 #ifndef ERD_WINO_NCH
@@ -152,6 +153,75 @@ struct WinoItem {
     int yl, xl;                         // output pixels at or beyond (yl, xl) are not this item's to store
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// What the kernels below share: wino_decode / wino_claim / wino_rearm (item list: all three), wino_item_geometry (data waves of
+// wino_conv_kernel and wino_x3_kernel) and, further down, wino_put_limbs (limb split of the two three-limb kernels).  Everything is
+// forced inline, and the device assembly of every kernel is what it was when these were lambdas pasted into each of them.  That is
+// the rule for adding to this list: compile before and after with the Makefile's flags and diff the assembly.  It holds only while
+// the kernels' scalars reach a helper BY REFERENCE, as a [&] lambda captures them (by value the register allocation of all three
+// kernels moves), and wino_conv_kernel additionally keeps one-line forwarding lambdas.  The epilogues, the column-sum reduction and
+// the rest of the data side were tried as functions too: same operations, but other schedules, so they stay in their kernels.
+
+// item number -> where it lives; CB = output channels per item (BN or BNP)
+template <int CB>
+__device__ __forceinline__ WinoItem wino_decode(const WinoDesc& p, int item) {
+    WinoItem it;
+    const int nb = item / p.blocks_per_nb;
+    int b = item - nb * p.blocks_per_nb;
+    int r = 0;
+    while (r + 1 < p.nreg && b >= p.reg[r + 1].block0) ++r;
+    const WinoRegion& rg = p.reg[r];
+    b -= rg.block0;
+    const int per_img = rg.nby * rg.nbx;
+    const int n = b / per_img;
+    const int rem = b - n * per_img;
+    const int by = rem / rg.nbx, bx = rem - by * rg.nbx;
+    const int lbw = rg.lbw;
+    it.s = __builtin_amdgcn_readfirstlane(rg.seg);
+    it.n = __builtin_amdgcn_readfirstlane(n);
+    it.y0 = __builtin_amdgcn_readfirstlane(2 * (rg.ty0 + by * (32 >> lbw)));
+    it.x0 = __builtin_amdgcn_readfirstlane(2 * (rg.tx0 + (bx << lbw)));
+    it.cout0 = __builtin_amdgcn_readfirstlane(nb * CB);
+    it.lbw = __builtin_amdgcn_readfirstlane(lbw);
+    it.yl = __builtin_amdgcn_readfirstlane(min(p.seg[rg.seg].H, 2 * rg.ty1));
+    it.xl = __builtin_amdgcn_readfirstlane(min(p.seg[rg.seg].W, 2 * rg.tx1));
+    return it;
+}
+// item k + 1 of this workgroup's sequence: claimed from the launch's counter, or (no counter) a static stride
+__device__ __forceinline__ int wino_claim(const WinoDesc& p, int k) {
+    return p.sched ? (int)gridDim.x + atomicAdd(p.sched, 1) : (int)blockIdx.x + (k + 1) * (int)gridDim.x;
+}
+// Data waves of the role-split kernels, on entering an item: the buffer resource of its input map, this thread's NCH raw-patch offsets
+// and its three patch rows g0..g2 (LDS bytes inside a raw buffer).
+__device__ __forceinline__ void wino_item_geometry(const WinoDesc& p, const int& Cin, const int& dt, const int& t_chunk, const int& t_tile,
+                                                   const int& t_half, const WinoItem& it, unsigned (&ro)[NCH], unsigned& g0,
+                                                   unsigned& g1, unsigned& g2, __amdgpu_buffer_rsrc_t& rs) {
+    const WinoSeg& sg = p.seg[it.s];
+    rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sg.in), 0, (int)((long long)sg.N * sg.in_nstride * 4), 0x00020000);
+    const int lbw = it.lbw, bw = 1 << lbw, bh = 32 >> lbw;
+    const int pc_n = 2 * bw + 2, npix = (2 * bh + 2) * pc_n;
+    const int recip = (65536 + pc_n - 1) / pc_n;              // (scalar)
+    const unsigned base_n = (unsigned)(it.n * sg.in_nstride);
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int idx = dt + 256 * i;
+        const int chunk = idx & 3, pix = idx >> 2;
+        const int pr = (pix * recip) >> 16, pc = pix - pr * pc_n;         // = pix / pc_n for pix < 512 (checked for every pitch)
+        const int iy = it.y0 - 1 + pr, ix = it.x0 - 1 + pc;
+        ro[i] = OOBV;
+        if (pix < npix && (unsigned)iy < (unsigned)sg.H && (unsigned)ix < (unsigned)sg.W)
+            ro[i] = (base_n + (unsigned)((iy * sg.W + ix) * Cin + chunk * 4)) * 4u;       // (< 2^31: checked by the host)
+    }
+    const int t_ty = t_tile >> lbw, t_tx = t_tile & (bw - 1);
+    g0 = (unsigned)((((2 * t_ty + t_half) * pc_n + 2 * t_tx) * RCS + t_chunk) * 16);
+    g1 = g0 + (unsigned)(pc_n * RCS * 16);
+    g2 = g1 + (unsigned)(pc_n * RCS * 16);
+}
+// exit of a workgroup (one thread calls it): the last workgroup to leave re-arms the counters
+__device__ __forceinline__ void wino_rearm(const WinoDesc& p) {
+    if (atomicAdd(p.sched + 1, 1) == (int)gridDim.x - 1) { p.sched[0] = 0; p.sched[1] = 0; }
+}
+
 __global__ __launch_bounds__(512, 2) void wino_conv_kernel(const WinoDesc p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // LDS: raw0 | raw1 (2 x [MAXPIX pixel slots][RCS] float4) | V0 | V1 (2 x [16][32 tiles][KS/4] float4, swizzled) |
@@ -166,34 +236,10 @@ __global__ __launch_bounds__(512, 2) void wino_conv_kernel(const WinoDesc p) {
     const int nitems = p.nitems;
     const int ncb16 = (p.Cout + 15) / 16;
 
-    auto decode = [&](int item) {
-        WinoItem it;
-        const int nb = item / p.blocks_per_nb;
-        int b = item - nb * p.blocks_per_nb;
-        int r = 0;
-        while (r + 1 < p.nreg && b >= p.reg[r + 1].block0) ++r;
-        const WinoRegion& rg = p.reg[r];
-        b -= rg.block0;
-        const int per_img = rg.nby * rg.nbx;
-        const int n = b / per_img;
-        const int rem = b - n * per_img;
-        const int by = rem / rg.nbx, bx = rem - by * rg.nbx;
-        const int lbw = rg.lbw;
-        it.s = __builtin_amdgcn_readfirstlane(rg.seg);
-        it.n = __builtin_amdgcn_readfirstlane(n);
-        it.y0 = __builtin_amdgcn_readfirstlane(2 * (rg.ty0 + by * (32 >> lbw)));
-        it.x0 = __builtin_amdgcn_readfirstlane(2 * (rg.tx0 + (bx << lbw)));
-        it.cout0 = __builtin_amdgcn_readfirstlane(nb * BN);
-        it.lbw = __builtin_amdgcn_readfirstlane(lbw);
-        it.yl = __builtin_amdgcn_readfirstlane(min(p.seg[rg.seg].H, 2 * rg.ty1));
-        it.xl = __builtin_amdgcn_readfirstlane(min(p.seg[rg.seg].W, 2 * rg.tx1));
-        return it;
-    };
-    // item k + 1 of this workgroup's sequence: claimed from the launch's counter, or (no counter) a static stride
-    auto claim = [&](int k) -> int {
-        return p.sched ? (int)gridDim.x + atomicAdd(p.sched, 1) : (int)blockIdx.x + (k + 1) * (int)gridDim.x;
-    };
 
+    // (forwarding lambdas, here and for item_geometry below: with direct calls this kernel's registers are allocated differently)
+    auto decode = [&](int item) { return wino_decode<BN>(p, item); };
+    auto claim = [&](int k) -> int { return wino_claim(p, k); };
     // waves 0-3 move data, waves 4-7 issue MFMAs; every SIMD hosts one wave of each kind
     const int wave_id = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const bool is_mma = wave_id >= 4;
@@ -414,9 +460,7 @@ __global__ __launch_bounds__(512, 2) void wino_conv_kernel(const WinoDesc p) {
                     g_wino_trace[blockIdx.x * 8 + 3] = (unsigned long long)(k_item + 1);
                 }
 #endif
-                if (wave == 0 && lane == 0 && p.sched) {     // the last workgroup to leave re-arms the counters
-                    if (atomicAdd(p.sched + 1, 1) == (int)gridDim.x - 1) { p.sched[0] = 0; p.sched[1] = 0; }
-                }
+                if (wave == 0 && lane == 0 && p.sched) wino_rearm(p);
                 break;
             }
             cur = nxt;
@@ -462,28 +506,8 @@ __global__ __launch_bounds__(512, 2) void wino_conv_kernel(const WinoDesc p) {
         bool nx_valid = false;
         unsigned nx_roff[NCH], nx_rd0 = 0, nx_rd1 = 0, nx_rd2 = 0;
         __amdgpu_buffer_rsrc_t nx_rs = rs_in;
-        auto item_geometry = [&](const WinoItem& it, unsigned (&ro)[NCH], unsigned& g0, unsigned& g1, unsigned& g2,
-                                 __amdgpu_buffer_rsrc_t& rs) {
-            const WinoSeg& sg = p.seg[it.s];
-            rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sg.in), 0, (int)((long long)sg.N * sg.in_nstride * 4), 0x00020000);
-            const int lbw = it.lbw, bw = 1 << lbw, bh = 32 >> lbw;
-            const int pc_n = 2 * bw + 2, npix = (2 * bh + 2) * pc_n;
-            const int recip = (65536 + pc_n - 1) / pc_n;              // (scalar)
-            const unsigned base_n = (unsigned)(it.n * sg.in_nstride);
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                const int idx = dt + 256 * i;
-                const int chunk = idx & 3, pix = idx >> 2;
-                const int pr = (pix * recip) >> 16, pc = pix - pr * pc_n;         // = pix / pc_n for pix < 512 (checked for every pitch)
-                const int iy = it.y0 - 1 + pr, ix = it.x0 - 1 + pc;
-                ro[i] = OOBV;
-                if (pix < npix && (unsigned)iy < (unsigned)sg.H && (unsigned)ix < (unsigned)sg.W)
-                    ro[i] = (base_n + (unsigned)((iy * sg.W + ix) * Cin + chunk * 4)) * 4u;       // (< 2^31: checked by the host)
-            }
-            const int t_ty = t_tile >> lbw, t_tx = t_tile & (bw - 1);
-            g0 = (unsigned)((((2 * t_ty + t_half) * pc_n + 2 * t_tx) * RCS + t_chunk) * 16);
-            g1 = g0 + (unsigned)(pc_n * RCS * 16);
-            g2 = g1 + (unsigned)(pc_n * RCS * 16);
+        auto item_geometry = [&](const WinoItem& it, unsigned (&ro)[NCH], unsigned& g0, unsigned& g1, unsigned& g2, __amdgpu_buffer_rsrc_t& rs) {
+            wino_item_geometry(p, Cin, dt, t_chunk, t_tile, t_half, it, ro, g0, g1, g2, rs);
         };
         // its scale / shift slice and the claim of the following item are REQUESTED on entry and written to LDS one slice
         // later (flush_pending, after the wait the raw slice needs anyway): neither the atomic's round trip nor the two
@@ -671,7 +695,8 @@ __global__ __launch_bounds__(512, 2) void wino_conv_kernel(const WinoDesc p) {
 //     (position, limb);
 //   * weight fragments: U3[position][limb][cout block][slice] is 1 KB contiguous; a ring of FOUR positions (x 3 limbs),
 //     re-loaded four positions ahead.
-// Everything else -- item list, block shapes, raw staging, look-ahead, the single barrier per slice -- is the fp32 kernel's.
+// Everything else -- item list (wino_decode, wino_claim), block shapes, raw staging (wino_item_geometry), look-ahead, the single
+// barrier per slice -- is the fp32 kernel's.
 constexpr int VX_B = 16 * 3 * 1024;            // bytes of one V buffer (three-limb form)
 #ifndef ERD_WX3_RD
 #define ERD_WX3_RD 4                          // weight-fragment ring depth in positions (4: half a slice ahead; 8: a whole slice)
@@ -679,6 +704,27 @@ constexpr int VX_B = 16 * 3 * 1024;            // bytes of one V buffer (three-l
 constexpr int XCH_B = 1024;                    // bytes of one exchange chunk (4 registers x 64 lanes)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// four channels of one position -> three limb words of 8 bytes, 1 KB apart (the three-limb kernels' V planes)
+__device__ __forceinline__ void wino_put_limbs(char* dst, const float4 v) {
+    uint2 hi, mid, lo;
+#ifdef ERD_WX3_NOSPLIT      // timing probe (tools/build_probe.sh): what the limb split costs the data side (results are wrong); like
+                            // ERD_WX3_VWRITE1 below it now acts on both three-limb kernels
+    hi.x = __builtin_amdgcn_perm(__float_as_uint(v.y), __float_as_uint(v.x), 0x07060302u);
+    hi.y = __builtin_amdgcn_perm(__float_as_uint(v.w), __float_as_uint(v.z), 0x07060302u);
+    mid = hi; lo = hi;
+#else
+    erd::limbs3_pair(v.x, v.y, hi.x, mid.x, lo.x);
+    erd::limbs3_pair(v.z, v.w, hi.y, mid.y, lo.y);
+#endif
+    *reinterpret_cast<uint2*>(dst) = hi;
+#ifdef ERD_WX3_VWRITE1     // timing probe: only the first limb is stored (results are wrong)
+    asm volatile("" :: "v"(mid.x), "v"(mid.y), "v"(lo.x), "v"(lo.y));
+#else
+    *reinterpret_cast<uint2*>(dst + 1024) = mid;
+    *reinterpret_cast<uint2*>(dst + 2048) = lo;
+#endif
+}
 
 __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -694,32 +740,6 @@ __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
     const int nitems = p.nitems;
     const int ncb32 = (p.Cout + 31) / 32;
 
-    auto decode = [&](int item) {
-        WinoItem it;
-        const int nb = item / p.blocks_per_nb;
-        int b = item - nb * p.blocks_per_nb;
-        int r = 0;
-        while (r + 1 < p.nreg && b >= p.reg[r + 1].block0) ++r;
-        const WinoRegion& rg = p.reg[r];
-        b -= rg.block0;
-        const int per_img = rg.nby * rg.nbx;
-        const int n = b / per_img;
-        const int rem = b - n * per_img;
-        const int by = rem / rg.nbx, bx = rem - by * rg.nbx;
-        const int lbw = rg.lbw;
-        it.s = __builtin_amdgcn_readfirstlane(rg.seg);
-        it.n = __builtin_amdgcn_readfirstlane(n);
-        it.y0 = __builtin_amdgcn_readfirstlane(2 * (rg.ty0 + by * (32 >> lbw)));
-        it.x0 = __builtin_amdgcn_readfirstlane(2 * (rg.tx0 + (bx << lbw)));
-        it.cout0 = __builtin_amdgcn_readfirstlane(nb * BN);
-        it.lbw = __builtin_amdgcn_readfirstlane(lbw);
-        it.yl = __builtin_amdgcn_readfirstlane(min(p.seg[rg.seg].H, 2 * rg.ty1));
-        it.xl = __builtin_amdgcn_readfirstlane(min(p.seg[rg.seg].W, 2 * rg.tx1));
-        return it;
-    };
-    auto claim = [&](int k) -> int {
-        return p.sched ? (int)gridDim.x + atomicAdd(p.sched, 1) : (int)blockIdx.x + (k + 1) * (int)gridDim.x;
-    };
 
     const int wave_id = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const bool is_mma = wave_id >= 4;
@@ -745,7 +765,7 @@ __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
         const char* const xpartner = smem + XOFF + (wave ^ 1) * 2 * XCH_B + lane * 16;
         int xr = 0;                                                                 // exchange rounds done
 
-        WinoItem cur = decode(item0);
+        WinoItem cur = wino_decode<BN>(p, item0);
         int k_item = 0;
         unsigned long long t_bar = 0, t_out = 0, t_xch = 0; (void)t_bar; (void)t_out; (void)t_xch;
         ERD_T0(t_begin);
@@ -768,7 +788,7 @@ __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
         for (;;) {
             const int nxt_item = __builtin_amdgcn_readfirstlane(sh_item[(k_item + 1) & 1]);
             const bool has_next = nxt_item < nitems;
-            const WinoItem nxt = has_next ? decode(nxt_item) : cur;
+            const WinoItem nxt = has_next ? wino_decode<BN>(p, nxt_item) : cur;
             const unsigned u_next = (unsigned)__builtin_amdgcn_readfirstlane(((nxt.cout0 >> 5) + cb) * nks * 1024);
 #pragma unroll
             for (int q = 0; q < 8; ++q)
@@ -936,9 +956,7 @@ __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
                     g_wino_trace[blockIdx.x * 8 + 3] = t_xch;             // (x3: the exchange polls inside the output stage, not the item count)
                 }
 #endif
-                if (wave == 0 && lane == 0 && p.sched) {     // the last workgroup to leave re-arms the counters
-                    if (atomicAdd(p.sched + 1, 1) == (int)gridDim.x - 1) { p.sched[0] = 0; p.sched[1] = 0; }
-                }
+                if (wave == 0 && lane == 0 && p.sched) wino_rearm(p);
                 break;
             }
             cur = nxt;
@@ -951,7 +969,7 @@ __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
         __builtin_amdgcn_s_setprio(ERD_WINO_DATA_PRIO);
         const int dt = tid & 255;
         const int t_chunk = dt & 3, t_tile = (dt >> 2) & 31, t_half = __builtin_amdgcn_readfirstlane(dt >> 7);
-        WinoItem la = decode(item0);
+        WinoItem la = wino_decode<BN>(p, item0);
         unsigned long long t_bar = 0, t_ent = 0, t_wait = 0; (void)t_bar; (void)t_ent; (void)t_wait;
         ERD_T0(t_begin);
         int la_ks = 0, k_la = 0;
@@ -970,36 +988,13 @@ __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
         bool nx_valid = false;
         unsigned nx_roff[NCH], nx_rd0 = 0, nx_rd1 = 0, nx_rd2 = 0;
         __amdgpu_buffer_rsrc_t nx_rs = rs_in;
-        auto item_geometry = [&](const WinoItem& it, unsigned (&ro)[NCH], unsigned& g0, unsigned& g1, unsigned& g2,
-                                 __amdgpu_buffer_rsrc_t& rs) {
-            const WinoSeg& sg = p.seg[it.s];
-            rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sg.in), 0, (int)((long long)sg.N * sg.in_nstride * 4), 0x00020000);
-            const int lbw = it.lbw, bw = 1 << lbw, bh = 32 >> lbw;
-            const int pc_n = 2 * bw + 2, npix = (2 * bh + 2) * pc_n;
-            const int recip = (65536 + pc_n - 1) / pc_n;
-            const unsigned base_n = (unsigned)(it.n * sg.in_nstride);
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                const int idx = dt + 256 * i;
-                const int chunk = idx & 3, pix = idx >> 2;
-                const int pr = (pix * recip) >> 16, pc = pix - pr * pc_n;
-                const int iy = it.y0 - 1 + pr, ix = it.x0 - 1 + pc;
-                ro[i] = OOBV;
-                if (pix < npix && (unsigned)iy < (unsigned)sg.H && (unsigned)ix < (unsigned)sg.W)
-                    ro[i] = (base_n + (unsigned)((iy * sg.W + ix) * Cin + chunk * 4)) * 4u;
-            }
-            const int t_ty = t_tile >> lbw, t_tx = t_tile & (bw - 1);
-            g0 = (unsigned)((((2 * t_ty + t_half) * pc_n + 2 * t_tx) * RCS + t_chunk) * 16);
-            g1 = g0 + (unsigned)(pc_n * RCS * 16);
-            g2 = g1 + (unsigned)(pc_n * RCS * 16);
-        };
         auto request_item_data = [&]() {
             if (dt < 64) {
                 const int co = la.cout0 + dt;
                 pend_sc = (p.scale && co < p.Cout) ? p.scale[co] : 1.f;
                 pend_sh = (p.shift && co < p.Cout) ? p.shift[co] : 0.f;
             }
-            if (dt == 64) pend_claim = claim(k_la);
+            if (dt == 64) pend_claim = wino_claim(p, k_la);
             pend_k = k_la;
         };
         auto flush_pending = [&]() {
@@ -1027,9 +1022,9 @@ __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
                 if (la_ks == 3) {
                     const int nx = __builtin_amdgcn_readfirstlane(sh_item[(k_la + 1) & 1]);
                     nx_valid = nx < nitems;
-                    if (nx_valid) nx_it = decode(nx);
+                    if (nx_valid) nx_it = wino_decode<BN>(p, nx);
                 }
-                if (la_ks == 4 && nx_valid) item_geometry(nx_it, nx_roff, nx_rd0, nx_rd1, nx_rd2, nx_rs);
+                if (la_ks == 4 && nx_valid) wino_item_geometry(p, Cin, dt, t_chunk, t_tile, t_half, nx_it, nx_roff, nx_rd0, nx_rd1, nx_rd2, nx_rs);
                 if (la_ks == nks) {
                     if (nx_valid) {
                         la = nx_it;
@@ -1058,24 +1053,6 @@ __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
             constexpr unsigned PAR = decltype(par_tag)::value;
 #pragma unroll
             for (int i = 0; i < NCH; ++i) *reinterpret_cast<float4*>(sm + PAR * RAWB + st_base + i * (64 * RCS * 16)) = src[i];
-        };
-        auto put = [&](char* dst, const float4 v) {        // four channels of one position -> three limb words of 8 bytes
-            uint2 hi, mid, lo;
-#ifdef ERD_WX3_NOSPLIT      // timing probe (tools/build_probe.sh): what the limb split costs the data waves (results are wrong)
-            hi.x = __builtin_amdgcn_perm(__float_as_uint(v.y), __float_as_uint(v.x), 0x07060302u);
-            hi.y = __builtin_amdgcn_perm(__float_as_uint(v.w), __float_as_uint(v.z), 0x07060302u);
-            mid = hi; lo = hi;
-#else
-            erd::limbs3_pair(v.x, v.y, hi.x, mid.x, lo.x);
-            erd::limbs3_pair(v.z, v.w, hi.y, mid.y, lo.y);
-#endif
-            *reinterpret_cast<uint2*>(dst) = hi;
-#ifdef ERD_WX3_VWRITE1     // timing probe: only the first limb is stored (results are wrong)
-            asm volatile("" :: "v"(mid.x), "v"(mid.y), "v"(lo.x), "v"(lo.y));
-#else
-            *reinterpret_cast<uint2*>(dst + 1024) = mid;
-            *reinterpret_cast<uint2*>(dst + 2048) = lo;
-#endif
         };
         // the transform in two halves so that its 12 LDS reads can be issued BEFORE the raw store / next loads of the same
         // iteration (they touch the other raw buffer) and travel under them: (1) the patch rows of this thread's (tile, 4 channels)
@@ -1112,10 +1089,10 @@ __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
 #pragma unroll
             for (int a = 0; a < 2; ++a) {                  // positions (2 HALF + a) * 4 + {0, 1, 2, 3}: 3 KB apart
                 char* v = sm + wr_base + VPAR * VB + ((2 * HALF + a) * 4) * 3 * 1024;
-                put(v + 0 * 3072, f4sub(rr[a][0], rr[a][2]));
-                put(v + 1 * 3072, f4add(rr[a][1], rr[a][2]));
-                put(v + 2 * 3072, f4sub(rr[a][2], rr[a][1]));
-                put(v + 3 * 3072, f4sub(rr[a][1], rr[a][3]));
+                wino_put_limbs(v + 0 * 3072, f4sub(rr[a][0], rr[a][2]));
+                wino_put_limbs(v + 1 * 3072, f4add(rr[a][1], rr[a][2]));
+                wino_put_limbs(v + 2 * 3072, f4sub(rr[a][2], rr[a][1]));
+                wino_put_limbs(v + 3 * 3072, f4sub(rr[a][1], rr[a][3]));
             }
         };
         using P0 = std::integral_constant<unsigned, 0>;
@@ -1123,7 +1100,7 @@ __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
         auto run = [&](auto half_tag) {
 #pragma unroll
             for (int i = 0; i < NCH; ++i) { rv[i] = make_float4(0.f, 0.f, 0.f, 0.f); rvb[i] = rv[i]; }
-            item_geometry(la, roff, nrd0, nrd1, nrd2, rs_in);
+            wino_item_geometry(p, Cin, dt, t_chunk, t_tile, t_half, la, roff, nrd0, nrd1, nrd2, rs_in);
             request_item_data();
             rd0 = nrd0;
             rd1 = nrd1;
@@ -1207,7 +1184,6 @@ __global__ __launch_bounds__(512, 2) void wino_x3_kernel(const WinoDesc p) {
 // 6 x 4 KB per cout pair, a barrier behind the writes and one behind the reads) instead of wino_x3_kernel's flag-polled
 // four-register rounds.  Same V values, same MFMA sequence per accumulator, same order of every sum: results are BIT-identical
 // to wino_x3_kernel (tests/test_gpu_wino_x3.py).
-constexpr int BNP = 128;                       // output channels per item
 constexpr int HPIX = 208;                      // raw pixel slots (the largest patch, 6 x 34, needs 204)
 
 __global__ __launch_bounds__(512, 2) void wino_x3p_kernel(const WinoDesc p) {
@@ -1226,32 +1202,6 @@ __global__ __launch_bounds__(512, 2) void wino_x3p_kernel(const WinoDesc p) {
     const int ncb32 = (p.Cout + 31) / 32;
     int cur_item = blockIdx.x;
 
-    auto decode = [&](int item) {
-        WinoItem it;
-        const int nb = item / p.blocks_per_nb;
-        int b = item - nb * p.blocks_per_nb;
-        int r = 0;
-        while (r + 1 < p.nreg && b >= p.reg[r + 1].block0) ++r;
-        const WinoRegion& rg = p.reg[r];
-        b -= rg.block0;
-        const int per_img = rg.nby * rg.nbx;
-        const int n = b / per_img;
-        const int rem = b - n * per_img;
-        const int by = rem / rg.nbx, bx = rem - by * rg.nbx;
-        const int lbw = rg.lbw;
-        it.s = __builtin_amdgcn_readfirstlane(rg.seg);
-        it.n = __builtin_amdgcn_readfirstlane(n);
-        it.y0 = __builtin_amdgcn_readfirstlane(2 * (rg.ty0 + by * (32 >> lbw)));
-        it.x0 = __builtin_amdgcn_readfirstlane(2 * (rg.tx0 + (bx << lbw)));
-        it.cout0 = __builtin_amdgcn_readfirstlane(nb * BNP);
-        it.lbw = __builtin_amdgcn_readfirstlane(lbw);
-        it.yl = __builtin_amdgcn_readfirstlane(min(p.seg[rg.seg].H, 2 * rg.ty1));
-        it.xl = __builtin_amdgcn_readfirstlane(min(p.seg[rg.seg].W, 2 * rg.tx1));
-        return it;
-    };
-    auto claim = [&](int k) -> int {
-        return p.sched ? (int)gridDim.x + atomicAdd(p.sched, 1) : (int)blockIdx.x + (k + 1) * (int)gridDim.x;
-    };
 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int item0 = blockIdx.x;
@@ -1273,7 +1223,7 @@ __global__ __launch_bounds__(512, 2) void wino_x3p_kernel(const WinoDesc p) {
     const unsigned pos0_b = (unsigned)(ri * 4 * 3) * per_xl_b;                  // this wave's first position
     const unsigned cb_b = (unsigned)nks * 1024u;                                // bytes from a cout block to the next inside a plane
     const unsigned v_lane = (unsigned)(ri * 4 * 3 * 1024 + h * 512 + ((li ^ (h * 8)) * 16));
-    WinoItem cur = decode(item0);
+    WinoItem cur = wino_decode<BNP>(p, item0);
     int k_item = 0;
     unsigned u_item = (unsigned)__builtin_amdgcn_readfirstlane(((cur.cout0 >> 5) + 2 * cp) * nks * 1024);
     // unit u = 2 j + b: position 4 ri + j, cout block 2 cp + b
@@ -1329,7 +1279,7 @@ __global__ __launch_bounds__(512, 2) void wino_x3p_kernel(const WinoDesc p) {
             pe.sc = (p.scale && co < p.Cout) ? p.scale[co] : 1.f;
             pe.sh = (p.shift && co < p.Cout) ? p.shift[co] : 0.f;
         }
-        if (tid == BNP) pe.claim = claim(k_la);
+        if (tid == BNP) pe.claim = wino_claim(p, k_la);
         pe.k = k_la;
     };
     auto flush_pending = [&](const Pending& pe) {
@@ -1356,7 +1306,7 @@ __global__ __launch_bounds__(512, 2) void wino_x3p_kernel(const WinoDesc p) {
         if (la_valid && la_ks == nks) {                   // the pointer leaves item k_la (its successor was claimed >= 3 slices ago)
             const int nx = __builtin_amdgcn_readfirstlane(sh_item[(k_la + 1) & 1]);
             if (nx < nitems) {
-                la = decode(nx);
+                la = wino_decode<BNP>(p, nx);
                 item_geometry(la, roff, nrdA, nrdB, rs_in);
                 la_ks = 0;
                 la_soff = 0;
@@ -1398,14 +1348,6 @@ __global__ __launch_bounds__(512, 2) void wino_x3p_kernel(const WinoDesc p) {
         const int c = t & 3, tl = (t >> 2) & 31;
         return VOFF + (unsigned)(t_row * 4 * 3072 + (c >> 1) * 512 + ((tl ^ ((c >> 1) * 8)) * 16) + (c & 1) * 8);
     };
-    auto put = [&](char* dst, const float4 v) {        // four channels of one position -> three limb words of 8 bytes
-        uint2 hi, mid, lo;
-        erd::limbs3_pair(v.x, v.y, hi.x, mid.x, lo.x);
-        erd::limbs3_pair(v.z, v.w, hi.y, mid.y, lo.y);
-        *reinterpret_cast<uint2*>(dst) = hi;
-        *reinterpret_cast<uint2*>(dst + 1024) = mid;
-        *reinterpret_cast<uint2*>(dst + 2048) = lo;
-    };
     // D phase: raw(g+1) -> V(g+1) (this thread's row of four positions), raw(g+2) regs -> LDS over raw(g), request raw(g+3) (last)
     // row pass of B^T d B for this wave's transform row (uniform branch: a packed add or a packed subtract, no sign operand)
     auto row_pass = [&](float4 (&R)[4]) __attribute__((always_inline)) {
@@ -1432,10 +1374,10 @@ __global__ __launch_bounds__(512, 2) void wino_x3p_kernel(const WinoDesc p) {
         float4 R[4];
         row_pass(R);
         char* v = sm + v_write_base() + npar * VB;
-        put(v + 0 * 3072, f4sub(R[0], R[2]));
-        put(v + 1 * 3072, f4add(R[1], R[2]));
-        put(v + 2 * 3072, f4sub(R[2], R[1]));
-        put(v + 3 * 3072, f4sub(R[1], R[3]));
+        wino_put_limbs(v + 0 * 3072, f4sub(R[0], R[2]));
+        wino_put_limbs(v + 1 * 3072, f4add(R[1], R[2]));
+        wino_put_limbs(v + 2 * 3072, f4sub(R[2], R[1]));
+        wino_put_limbs(v + 3 * 3072, f4sub(R[1], R[3]));
         __builtin_amdgcn_sched_barrier(0);
 #ifdef ERD_WINO_TRACE
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1654,10 +1596,10 @@ __global__ __launch_bounds__(512, 2) void wino_x3p_kernel(const WinoDesc p) {
         float4 R[4];
         row_pass(R);
         char* v = sm + v_write_base();
-        put(v + 0 * 3072, f4sub(R[0], R[2]));
-        put(v + 1 * 3072, f4add(R[1], R[2]));
-        put(v + 2 * 3072, f4sub(R[2], R[1]));
-        put(v + 3 * 3072, f4sub(R[1], R[3]));
+        wino_put_limbs(v + 0 * 3072, f4sub(R[0], R[2]));
+        wino_put_limbs(v + 1 * 3072, f4add(R[1], R[2]));
+        wino_put_limbs(v + 2 * 3072, f4sub(R[2], R[1]));
+        wino_put_limbs(v + 3 * 3072, f4sub(R[1], R[3]));
         store_raw(rvb, 1);
         issue_next(rv);                                   // raw(2)
         __syncthreads();                                  // V(0) complete, raw(1) in LDS
@@ -1671,7 +1613,7 @@ __global__ __launch_bounds__(512, 2) void wino_x3p_kernel(const WinoDesc p) {
     for (;;) {
         const int nxt_item = __builtin_amdgcn_readfirstlane(sh_item[(k_item + 1) & 1]);
         const bool has_next = nxt_item < nitems;
-        const WinoItem nxt = has_next ? decode(nxt_item) : cur;
+        const WinoItem nxt = has_next ? wino_decode<BNP>(p, nxt_item) : cur;
         const unsigned u_next = (unsigned)__builtin_amdgcn_readfirstlane(((nxt.cout0 >> 5) + 2 * cp) * nks * 1024);
 #pragma unroll
         for (int q = 0; q < 8; ++q)
@@ -1704,9 +1646,7 @@ __global__ __launch_bounds__(512, 2) void wino_x3p_kernel(const WinoDesc p) {
                 tr[7] = t_out;
             }
 #endif
-            if (tid == 0 && p.sched) {                       // the last workgroup to leave re-arms the counters
-                if (atomicAdd(p.sched + 1, 1) == (int)gridDim.x - 1) { p.sched[0] = 0; p.sched[1] = 0; }
-            }
+            if (tid == 0 && p.sched) wino_rearm(p);
             break;
         }
         cur = nxt;

@@ -98,3 +98,36 @@ def test_distillation_nms_kernel_fits_static_lds_and_uses_no_scratch(tmp_path):
     cap = int(re.search(r"constexpr int NMS_LDS_K = (\d+);", src).group(1))
     assert cap * (16 + 4 + 4 + 1) <= lds <= 65536, (cap, lds)
     assert scratch == 0
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_winograd_kernels_use_no_scratch_and_only_dynamic_lds(tmp_path):
+    """The three Winograd kernels (winograd.hip) keep ~250 VGPRs of state per thread -- accumulators, weight-fragment ring, the look-ahead
+    item's offsets -- and call shared forced-inline helpers that take that state by reference: a piece the compiler fails to break up into
+    registers becomes scratch memory, whose loads wait in the same in-order counter as the weight-fragment stream.  So: no scratch in any
+    of them, all LDS dynamic (the host sizes it per kernel), and the strict-fp32 kernel's vector work free of packed fp32 arithmetic
+    (-fno-slp-vectorize; the f32x16 output stages of the two three-limb kernels do hold packed operations: not a property to freeze)."""
+    import re
+    mk = open(os.path.join(ROOT, "erd_amd", "csrc", "Makefile")).read()
+    assert "GEMM_FLAGS := -fno-slp-vectorize" in mk and "winograd.o: " in mk
+    assert re.search(r"winograd\.o:[^\n]*\n\t\$\(HIPCC\) \$\(CXXFLAGS\) \$\(GEMM_FLAGS\) -c", mk)       # the flags below are the Makefile's for this file
+    out = tmp_path / "winograd.s"
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function", "-fno-slp-vectorize", "-S",
+                        "--cuda-device-only", "-o", str(out), "winograd.hip"], cwd=os.path.join(ROOT, "erd_amd", "csrc"),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    s = open(out).read()
+    seen = set()
+    for m in re.finditer(r"^(_Z\S+):[^\n]*\n(.*?)^\s*\.end_amdhsa_kernel", s, re.S | re.M):
+        name, body = m.group(1), m.group(2)
+        kern = next((k for k in ("wino_conv_kernel", "wino_x3_kernel", "wino_x3p_kernel") if k + "E" in name), None)
+        if kern is None:
+            continue
+        seen.add(kern)
+        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
+        assert int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1)) == 0, name
+        code = [t.strip() for t in body.split("\n") if t.strip() and not t.strip().startswith(";")]
+        assert not any(t.startswith("scratch_") for t in code), name
+        if kern == "wino_conv_kernel":
+            assert not any(re.match(r"v_pk_(add|mul|fma)_f32", t) for t in code), name
+    assert seen == {"wino_conv_kernel", "wino_x3_kernel", "wino_x3p_kernel"}, seen
