@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("ERD_HIP_LIB") or os.path.join(_HERE, "lib", "liberd_h
 
 ERD_MAX_SEG = 5
 ERD_MAX_TAPS = 9
+ERD_SQNORM_PARTS = 1024
 
 c_float_p = C.c_void_p  # raw device pointers travel as integers
 i64 = C.c_int64
@@ -113,6 +114,11 @@ _SIGNATURES = {
     "erd_level_scale": [P, P, P, i32, i64, i32, C.POINTER(Levels), P],
     "erd_level_scale_bwd": [P, P, P, P, P, i32, i64, i32, C.POINTER(Levels), P],
     "erd_sgd_momentum": [P, P, P, i64, f32, f32, f32, f32, i32, P],
+    "erd_sgd_groups_table": [P, P, P, i32, P, P],
+    "erd_sgd_momentum_groups": [P, P, P, i64, i64, P, i32, i32, i64, i64, f32, f32, f32, P, i32, P],
+    "erd_grad_sqnorm": [P, i64, P, P],
+    "erd_clip_coef": [P, i32, f32, f32, P, P],
+    "erd_grad_accumulate": [P, P, i64, i32, P],
     "erd_ers_select": [P, P, i32, i64, i32, i32, P, P, P, P, P, P, P, P],
     "erd_grid_anchors": [P, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, i32, P],
     "erd_atss_assign": [P, P, C.POINTER(i64), i32, i64, P, P, P, i32, i32, i32, i32, P, P, P, P, P, P],

@@ -2,6 +2,7 @@
 // forward/backward over level-concatenated [N][A][C] maps, FPN top-down add, bias/scale helpers, SGD.
 // All activations NHWC fp32; 16-byte (float4) accesses, channels fastest => fully coalesced rows.
 #include "erd_common.h"
+#include <vector>
 
 namespace erd {
 thread_local char g_err[512] = "";
@@ -694,6 +695,97 @@ __global__ __launch_bounds__(256) void sgd_kernel(float4* __restrict__ p, const 
     }
 }
 
+// ---- optimizer update with parameter groups, gradient clipping, gradient accumulation ---------------------------------
+// sgd_kernel with a segment table: entry s covers the elements [seg[s].begin, seg[s + 1].begin) of the flat buffers (absolute
+// offsets; `base` is where p / g / buf start), with the learning-rate multiplier and the ABSOLUTE weight decay of its parameter.
+// A block's 256 float4 are contiguous: the table is searched once per tile for the tile's first element (block-uniform loads),
+// each lane then walks forward to its own segment -- at most a few entries, segments start on multiples of 4 floats (in the
+// trainer: of 64).  Per element the operations and their order are sgd_kernel's.
+__global__ __launch_bounds__(256) void sgd_groups_kernel(float4* __restrict__ p, const float4* __restrict__ g,
+                                                         float4* __restrict__ buf, int64_t n4, int64_t base,
+                                                         const erd_sgd_seg* __restrict__ seg, int nseg, float lr0, float mom,
+                                                         float gs0, const float* __restrict__ coef, int first) {
+    const float gs = coef ? gs0 * coef[0] : gs0;
+    for (int64_t t0 = blockIdx.x * 256ll; t0 < n4; t0 += (int64_t)gridDim.x * 256) {
+        const int64_t e0 = base + t0 * 4;
+        int lo = 0, hi = nseg - 1;               // last entry whose begin <= e0 (the launcher checked seg[0].begin <= base)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (seg[mid].begin <= e0) lo = mid; else hi = mid - 1;
+        }
+        const int64_t i = t0 + threadIdx.x;
+        if (i >= n4) continue;
+        const int64_t e = base + i * 4;
+        int s = lo;
+        while (s + 1 < nseg && seg[s + 1].begin <= e) ++s;
+        const float lr = lr0 * seg[s].lr_mult, wd = seg[s].weight_decay;
+        float4 pp = p[i];
+        const float4 gg = g[i];
+        float4 d;
+        d.x = gg.x * gs + wd * pp.x; d.y = gg.y * gs + wd * pp.y;
+        d.z = gg.z * gs + wd * pp.z; d.w = gg.w * gs + wd * pp.w;
+        float4 b;
+        if (first) {
+            b = d;
+        } else {
+            b = buf[i];
+            b.x = mom * b.x + d.x; b.y = mom * b.y + d.y; b.z = mom * b.z + d.z; b.w = mom * b.w + d.w;
+        }
+        buf[i] = b;
+        pp.x -= lr * b.x; pp.y -= lr * b.y; pp.z -= lr * b.z; pp.w -= lr * b.w;
+        p[i] = pp;
+    }
+}
+
+// sum of squares of g[0, n) as ERD_SQNORM_PARTS fp64 partials: workgroup b owns the float4 b*256 + t + k*PARTS*256 (a partition
+// that depends on n alone), every lane accumulates the exact fp64 squares of its elements in index order, the lanes fold through
+// the wave butterfly and the four waves in order.  No float atomics: the same gradient gives the same bits on every run.
+__device__ __forceinline__ double block_sum_d(double acc) {
+    acc = erd::wave_sum_d(acc);
+    __shared__ double red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float4* __restrict__ g, int64_t n4, double* __restrict__ part) {
+    double acc = 0.0;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)ERD_SQNORM_PARTS * 256) {
+        const float4 v = g[i];
+        acc += (double)v.x * (double)v.x;
+        acc += (double)v.y * (double)v.y;
+        acc += (double)v.z * (double)v.z;
+        acc += (double)v.w * (double)v.w;
+    }
+    const double s = block_sum_d(acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void clip_coef_kernel(const double* __restrict__ part, int64_t nparts, float gs, float max_norm,
+                                                        float* __restrict__ out) {
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < nparts; i += 256) acc += part[i];
+    const double s = block_sum_d(acc);
+    if (threadIdx.x == 0) {
+        const float total = (float)((double)gs * sqrt(s));
+        const float c = max_norm / (total + 1e-6f);
+        out[0] = total;
+        out[1] = c < 1.f ? c : 1.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float4* __restrict__ acc, const float4* __restrict__ g, int64_t n4,
+                                                              int first) {
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        float4 a = g[i];
+        if (!first) {
+            const float4 o = acc[i];
+            a.x = o.x + a.x; a.y = o.y + a.y; a.z = o.z + a.z; a.w = o.w + a.w;
+        }
+        acc[i] = a;
+    }
+}
+
 inline int grid_for(int64_t n, int cap = 2048) {
     int64_t b = (n + 255) / 256;
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
@@ -1031,4 +1123,72 @@ extern "C" int erd_sgd_momentum(float* p, const float* g, float* buf, int64_t n,
                        reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(buf),
                        n / 4, lr, momentum, weight_decay, grad_scale, first_step);
     return erd::check_launch("sgd");
+}
+
+// torch.optim.SGD with parameter groups (the reference builds them through mmengine's OptimWrapper / paramwise_cfg): validates a
+// host segment table and writes its device form, nseg + 1 entries (the last one is the end of the buffers)
+extern "C" int erd_sgd_groups_table(const int64_t* seg_off, const float* lr_mult, const float* weight_decay, int nseg,
+                                    erd_sgd_seg* table_dev, erd_stream_t stream) {
+    ERD_REQUIRE(seg_off && lr_mult && weight_decay && table_dev && nseg >= 1, "sgd_groups_table: bad args");
+    std::vector<erd_sgd_seg> host((size_t)nseg + 1);
+    for (int s = 0; s <= nseg; ++s) {
+        ERD_REQUIRE(seg_off[s] >= 0 && seg_off[s] % 4 == 0, "sgd_groups_table: segment %d starts at element %lld, not a multiple of 4 "
+                    "floats (a float4 would straddle two segments)", s, (long long)seg_off[s]);
+        ERD_REQUIRE(s == 0 || seg_off[s] > seg_off[s - 1], "sgd_groups_table: offsets must increase (segment %d)", s);
+        host[s].begin = seg_off[s];
+        host[s].lr_mult = s < nseg ? lr_mult[s] : 0.f;
+        host[s].weight_decay = s < nseg ? weight_decay[s] : 0.f;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(table_dev, host.data(), host.size() * sizeof(erd_sgd_seg), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);        // (`host` dies with this call; tables are built once per trainer)
+    if (e != hipSuccess) {
+        erd::set_error("sgd_groups_table: %s", hipGetErrorString(e));
+        return (int)e;
+    }
+    return 0;
+}
+
+// torch.optim.SGD with parameter groups over [base, base + n) of the flat buffers (p, g, buf point AT element `base`): segments
+// [seg0, seg0 + nseg) of the device table cover the range.  clip_coef: optional device float that multiplies grad_scale
+// (torch.nn.utils.clip_grad_norm_'s coefficient, erd_clip_coef)
+extern "C" int erd_sgd_momentum_groups(float* p, const float* g, float* buf, int64_t base, int64_t n, const erd_sgd_seg* table_dev,
+                                       int seg0, int nseg, int64_t seg0_begin, int64_t seg_end, float lr, float momentum,
+                                       float grad_scale, const float* clip_coef, int first_step, erd_stream_t stream) {
+    ERD_REQUIRE(p && g && buf && table_dev && n % 4 == 0 && base % 4 == 0 && n >= 0, "sgd_groups: bad args (base and n must be "
+                "multiples of 4)");
+    ERD_REQUIRE(seg0 >= 0 && nseg >= 1 && seg0_begin <= base && base + n <= seg_end, "sgd_groups: segments [%lld, %lld) do not cover "
+                "the range [%lld, %lld)", (long long)seg0_begin, (long long)seg_end, (long long)base, (long long)(base + n));
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(sgd_groups_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(buf), n / 4, base,
+                       table_dev + seg0, nseg, lr, momentum, grad_scale, clip_coef, first_step);
+    return erd::check_launch("sgd_groups");
+}
+
+// torch.nn.utils.clip_grad_norm_ (norm_type 2; the reference: OptimWrapper clip_grad), first half: the sum of squares of g[0, n) as
+// ERD_SQNORM_PARTS fp64 partials in the caller's slot (every entry of the slot is written)
+extern "C" int erd_grad_sqnorm(const float* g, int64_t n, double* partials, erd_stream_t stream) {
+    ERD_REQUIRE((g || n == 0) && partials && n >= 0 && n % 4 == 0, "grad_sqnorm: bad args (n must be a multiple of 4)");
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(ERD_SQNORM_PARTS), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(g), n / 4, partials);
+    return erd::check_launch("grad_sqnorm");
+}
+
+// ... second half: folds nslots slots in a fixed order, out[0] = total_norm = grad_scale * sqrt(sum) (the norm of the MEAN gradient),
+// out[1] = min(1, max_norm / (total_norm + 1e-6)); both stay on the device
+extern "C" int erd_clip_coef(const double* partials, int nslots, float grad_scale, float max_norm, float* out, erd_stream_t stream) {
+    ERD_REQUIRE(partials && out && nslots >= 1 && max_norm > 0.f, "clip_coef: bad args");
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (int64_t)nslots * ERD_SQNORM_PARTS,
+                       grad_scale, max_norm, out);
+    return erd::check_launch("clip_coef");
+}
+
+// OptimWrapper accumulative_counts: acc = g (first micro-step of a window) or acc += g, plain fp32 adds
+extern "C" int erd_grad_accumulate(float* acc, const float* g, int64_t n, int first, erd_stream_t stream) {
+    ERD_REQUIRE(acc && g && n >= 0 && n % 4 == 0, "grad_accumulate: bad args (n must be a multiple of 4)");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(grad_accumulate_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<float4*>(acc), reinterpret_cast<const float4*>(g), n / 4, first);
+    return erd::check_launch("grad_accumulate");
 }

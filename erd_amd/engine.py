@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from . import functional as Fn
 from . import kernels as K
+from . import optim_cfg as OC
 from .dist_utils import all_reduce_sum_
 from .modules import GFLIncrementERD, parse_losses
 from .structures import unpack_gt_instances
@@ -321,8 +322,17 @@ class ERDTrainer:
     def __init__(self, model: nn.Module, lr: float = 0.01, momentum: float = 0.9, weight_decay: float = 1e-4,
                  base_batch_size: int = 16, batch_size_per_gpu: Optional[int] = None, auto_scale_lr: bool = True,
                  warmup_iters: int = 500, warmup_start_factor: float = 0.001, bucket_mb: int = 32,
-                 overlap_teacher: bool = True, teacher_graph: bool = False, step_graph: bool = False):
+                 overlap_teacher: bool = True, teacher_graph: bool = False, step_graph: bool = False,
+                 paramwise_cfg: Optional[dict] = None, clip_grad: Optional[dict] = None, accumulative_counts: int = 1):
+        """paramwise_cfg / clip_grad / accumulative_counts: the `optim_wrapper` keys of those names (mmengine's OptimWrapper and
+        DefaultOptimWrapperConstructor; optim_cfg.py).  Without them the update is ONE scalar learning rate and weight decay
+        (erd_sgd_momentum) exactly as before; with any of them see _update_bucket_ext / _apply_pending_ext."""
         self.model = model
+        self.clip = OC.check_clip_grad(clip_grad)
+        self.accum = OC.check_accumulative_counts(accumulative_counts)
+        if step_graph and self.accum > 1:
+            raise NotImplementedError("accumulative_counts > 1 inside a captured whole-step graph is not built")
+        OC.check_paramwise(paramwise_cfg)
         self.distributed = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size() if self.distributed else 1
         self.cu_reserve = 0                  # CUs the grids leave to RCCL's resident kernels (tune_cu_reserve; 0 at one rank)
@@ -345,6 +355,24 @@ class ERDTrainer:
         self._pending_lr = self.base_lr
         self._first = True
         self._pending = False                # an un-applied gradient sits in flat.grad
+        # optim_wrapper options.  `resolved`: per-parameter lr multiplier / weight decay (model.parameters() order); `_table`: its
+        # device form, one segment per flat parameter (also built for clipping alone: the coefficient enters through the same
+        # kernel); `_acc`: the accumulation window's gradient sum (backward kernels need flat.grad zero at the start of every
+        # micro-step, functional._sink, so the window lives in a second flat buffer that the update reads instead)
+        self.resolved = (OC.resolve_paramwise(model, self.base_lr, weight_decay, paramwise_cfg)
+                         if paramwise_cfg is not None else None)
+        self._table = None
+        if self.resolved is not None or self.clip is not None:
+            index = {id(q): i for i, q in enumerate(model.parameters())}
+            rows = [self.resolved[index[id(q)]] if self.resolved is not None else dict(lr_mult=1.0, weight_decay=weight_decay)
+                    for q in self.flat.params]
+            self._table = K.SgdSegTable(self.flat.offsets + [self.flat.total], [r["lr_mult"] for r in rows],
+                                        [r["weight_decay"] for r in rows], dev)
+        self._acc = torch.zeros_like(self.flat.grad) if self.accum > 1 else None
+        self._ext = self._table is not None or self._acc is not None
+        self._window = 0                     # micro-steps whose gradient is in (or on its way into) `_acc` and not applied yet
+        self._micro_first, self._close, self._m = True, True, 1      # of the step being issued / pending (_plan_step)
+        self._norm_ws = self._norm_out = None
         self._teacher_ahead = None           # (inputs, TeacherOut) of the following step (train_step(next_batch=...))
         self.prefold = Fn.BnPrefold(model) if os.environ.get("ERD_BN_PREFOLD", "1") != "0" else None
         self.prep = K.ParamPrep(self.device) if os.environ.get("ERD_PARAM_PREP", "1") != "0" and self.prefold is not None else None
@@ -377,6 +405,9 @@ class ERDTrainer:
                                              stream=torch.cuda.Stream(device=dev), live_streams=live)
             else:
                 self.sync = BucketedGradSync(self.flat, streams=producers, live_streams=live)
+        if self.clip is not None:            # one slot of fp64 partials per bucket (the whole range uses the first one)
+            nslots = len(self.flat.buckets) if self.bucket_update else 1
+            self._norm_ws = torch.zeros(nslots * K._lib.ERD_SQNORM_PARTS, dtype=torch.float64, device=dev)
         self.side = torch.cuda.Stream(device=dev) if self.overlap_teacher else None
         # whole-step hipGraph (one per input shape): everything between two SGD updates -- teacher, ERS, NMS, targets,
         # student forward, losses, backward on all streams -- is recorded once and replayed as ONE launch; the step is
@@ -413,6 +444,8 @@ class ERDTrainer:
     def _update_bucket(self, b: int) -> None:
         """BucketedGradSync.on_bucket: the summed gradient of bucket b is final and every launch that reads the bucket's
         weights / folded scales / prepared buffers is queued ahead of the current (update) stream"""
+        if self._ext:
+            return self._update_bucket_ext(b)
         s, e, _ = self.flat.buckets[b]
         K.sgd_momentum_(self.flat.data[s:e], self.flat.grad[s:e], self.flat.momentum[s:e], self._pending_lr, self.momentum,
                         self.weight_decay, 1.0 / self.world, self._first)
@@ -423,11 +456,97 @@ class ERDTrainer:
         else:
             self.prep.invalidate()
 
+    # -- the update with optim_wrapper options (paramwise_cfg, clip_grad, accumulative_counts) ------------------------------
+    def _plan_step(self, log_vars) -> None:
+        """fixes what the update of the step being issued does BEFORE its backward pass (per-bucket updates start inside it):
+        first micro-step of a window or not, closing the window or not (mmengine: (iter + 1) % accumulative_counts == 0),
+        micro-steps in the window; with clipping a closing step logs `grad_norm`, a device float written by the update"""
+        if not self._ext:
+            return
+        self._micro_first = self._window == 0
+        self._window += 1
+        self._close, self._m = OC.should_update(self.iter, self.accum), self._window
+        if self._close:
+            self._window = 0
+            if self.clip is not None:
+                log_vars["grad_norm"] = self._new_norm_out()[0]
+
+    def _new_norm_out(self) -> Tensor:
+        """(total_norm, coefficient) of one update: a buffer per update, the log keeps reading the previous ones"""
+        self._norm_out = torch.empty(2, dtype=torch.float32, device=self.device)
+        if self.sync is not None and self.sync.stream is not None:
+            self._norm_out.record_stream(self.sync.stream)
+        return self._norm_out
+
+    def _update_range(self, b: Optional[int]) -> None:
+        """SGD on bucket b's slice (None: the whole buffers), then the derived state of that range: bf16 shadow, BN folds,
+        prepared weights.  Reads the window's sum when gradients are accumulated; grad_scale = 1 / (ranks * micro-steps)"""
+        s, e = (0, self.flat.total) if b is None else self.flat.buckets[b][:2]
+        g = self.flat.grad if self._acc is None else self._acc
+        scale = 1.0 / (self.world * self._m)
+        if self._table is None:
+            K.sgd_momentum_(self.flat.data[s:e], g[s:e], self.flat.momentum[s:e], self._pending_lr, self.momentum,
+                            self.weight_decay, scale, self._first)
+        else:
+            K.sgd_momentum_groups_(self.flat.data[s:e], g[s:e], self.flat.momentum[s:e], s, self._table, self._pending_lr,
+                                   self.momentum, scale, self._first, None if self.clip is None else self._norm_out[1:2])
+        self.flat.refresh_shadow(b)
+        if self.prefold is not None:
+            self.prefold.run() if b is None else self.prefold.run_group(b)
+        if self.prep is not None:
+            if self.prefold is not None and self.prefold.valid[0]:
+                self.prep.run() if b is None else self.prep.run_group(b)
+            else:
+                self.prep.invalidate()
+
+    def _apply_window(self) -> None:
+        """the update over the whole buffers on the current stream: [norm -> coefficient ->] SGD -> derived state"""
+        if self.clip is not None:
+            slot = self._norm_ws[:K._lib.ERD_SQNORM_PARTS]
+            K.grad_sqnorm_into(self.flat.grad if self._acc is None else self._acc, slot)
+            K.clip_coef_(slot, 1.0 / (self.world * self._m), self.clip["max_norm"], self._norm_out)
+        self._update_range(None)
+
+    def _update_bucket_ext(self, b: int) -> None:
+        """_update_bucket with options.  Accumulation: the bucket's summed gradient joins the window; a step that does not close
+        the window ends here.  Clipping: the coefficient needs EVERY bucket, so a bucket only queues the sum of squares of its
+        slice (behind its all-reduce, on the update stream); the last bucket -- released when the backward pass has ended, so
+        every launch that reads any weight is queued ahead -- adds the finalize and then updates all buckets."""
+        s, e, _ = self.flat.buckets[b]
+        if self._acc is not None:
+            K.grad_accumulate_(self._acc[s:e], self.flat.grad[s:e], self._micro_first)
+        if not self._close:
+            return
+        if self.clip is None:
+            self._update_range(b)
+            return
+        P = K._lib.ERD_SQNORM_PARTS
+        g = self.flat.grad if self._acc is None else self._acc
+        K.grad_sqnorm_into(g[s:e], self._norm_ws[b * P:(b + 1) * P])
+        if b == len(self.flat.buckets) - 1:
+            K.clip_coef_(self._norm_ws, 1.0 / (self.world * self._m), self.clip["max_norm"], self._norm_out)
+            for j in range(len(self.flat.buckets)):
+                self._update_range(j)
+
+    def _apply_pending_ext(self) -> None:
+        if self.sync is not None:
+            self.sync.wait()
+        if not self.bucket_update:
+            if self._acc is not None:
+                K.grad_accumulate_(self._acc, self.flat.grad, self._micro_first)
+            if self._close:
+                self._apply_window()
+        if self._close:
+            self._first = False
+        self._pending = False
+
     def _apply_pending(self) -> None:
         """wait for the bucket all-reduces of the previous backward, then ONE fused SGD launch -- or, with the per-bucket
         update, release the buckets that are left (the tail) and join the update stream."""
         if not self._pending:
             return
+        if self._ext:
+            return self._apply_pending_ext()
         if self.bucket_update:
             self.sync.wait()
             self._first = False
@@ -448,8 +567,16 @@ class ERDTrainer:
             else:
                 self.prep.invalidate()
 
-    def flush(self) -> None:
+    def flush(self, close_window: bool = True) -> None:
+        """apply what is pending.  With gradient accumulation this also closes the window: a partial window of m micro-steps is
+        applied with 1 / m (close_window=False only settles the last step: the runner's log read-back)"""
         self._apply_pending()
+        if close_window and self._ext and self._window > 0:
+            self._m, self._window = self._window, 0
+            if self.clip is not None:
+                self._new_norm_out()
+            self._apply_window()
+            self._first = False
 
     def tune_cu_reserve(self, batches, candidates: Sequence[int] = (0, 4, 8), steps: int = 3, timer=None) -> dict:
         """Data parallel only (a no-op report at one rank): the kernels' persistent / stream-K / one-round grids are whole-chip static
@@ -504,6 +631,8 @@ class ERDTrainer:
             for p, off in zip(self.flat.params, self.flat.offsets):
                 buf = _storage_view(self.flat.momentum, off, p)
                 state[index[id(p)]] = dict(momentum_buffer=buf.detach().cpu().contiguous().clone())
+        if self.resolved is not None:        # one group per parameter, as mmengine's constructor builds them
+            return dict(state=state, param_groups=OC.build_param_groups(self.resolved, self.last_lr, self.base_lr, self.momentum))
         group = dict(lr=self.last_lr, momentum=self.momentum, dampening=0, weight_decay=self.weight_decay, nesterov=False,
                      maximize=False, foreach=None, differentiable=False, initial_lr=self.base_lr,
                      params=list(range(len(index))))
@@ -660,6 +789,7 @@ class ERDTrainer:
             if log_vars is not None:
                 self._pending = True
                 self._pending_lr = self.last_lr = self.lr_at(self.iter, self.epoch_factor)
+                self._plan_step(log_vars)
                 self.iter += 1
                 return log_vars
         if self.overlap_teacher:
@@ -709,6 +839,7 @@ class ERDTrainer:
             with torch.cuda.stream(self.side), torch.no_grad():
                 self._teacher_ahead = (next_batch[0], self._teacher(next_batch[0], next_batch[1], self.iter + 1))
         self._pending_lr = self.last_lr = self.lr_at(self.iter, self.epoch_factor)      # (per-bucket updates start inside backward)
+        self._plan_step(log_vars)
         if self.sync is not None:
             self.sync.arm()
         total.backward()

@@ -1270,6 +1270,66 @@ def sgd_momentum_(p: Tensor, g: Tensor, buf: Tensor, lr: float, momentum: float,
          1 if first_step else 0, _stream())
 
 
+class SgdSegTable:
+    """Device segment table of erd_sgd_momentum_groups: one segment per parameter of the flat buffers (engine.FlatParams), with
+    its learning-rate multiplier and absolute weight decay.  `offsets`: nseg + 1 increasing element offsets, the last one the
+    end of the buffers; segment s owns [offsets[s], offsets[s + 1]) -- the zero padding behind its parameter included."""
+
+    def __init__(self, offsets, lr_mults, weight_decays, device):
+        import numpy as np
+        self.offsets = [int(o) for o in offsets]
+        self.nseg = len(self.offsets) - 1
+        if self.nseg < 1 or len(lr_mults) != self.nseg or len(weight_decays) != self.nseg:
+            raise ValueError("SgdSegTable: need nseg + 1 offsets and nseg multipliers / decays")
+        self.lr_mults, self.weight_decays = [float(v) for v in lr_mults], [float(v) for v in weight_decays]
+        off = np.asarray(self.offsets, dtype=np.int64)
+        lrm = np.asarray(self.lr_mults, dtype=np.float32)
+        wd = np.asarray(self.weight_decays, dtype=np.float32)
+        self.table = torch.empty((self.nseg + 1) * 16, dtype=torch.uint8, device=device)
+        call("erd_sgd_groups_table", off.ctypes.data, lrm.ctypes.data, wd.ctypes.data, self.nseg, _p(self.table), _stream())
+
+    def span(self, base: int, n: int):
+        """(first segment, segment count) covering the elements [base, base + n)"""
+        import bisect
+        s0 = bisect.bisect_right(self.offsets, base) - 1
+        s1 = bisect.bisect_left(self.offsets, base + n)
+        return s0, max(s1 - s0, 1)
+
+
+def sgd_momentum_groups_(p: Tensor, g: Tensor, buf: Tensor, base: int, table: SgdSegTable, lr: float, momentum: float,
+                         grad_scale: float, first_step: bool, clip_coef: Optional[Tensor] = None) -> None:
+    """torch.optim.SGD with parameter groups on the slices p, g, buf = flat[base:base + n] (one launch); clip_coef: ONE device
+    float that multiplies grad_scale (clip_coef_'s second output)"""
+    assert p.is_contiguous() and g.is_contiguous() and buf.is_contiguous() and p.numel() == g.numel() == buf.numel()
+    assert clip_coef is None or (clip_coef.dtype == torch.float32 and clip_coef.numel() == 1 and clip_coef.device == p.device)
+    n = p.numel()
+    s0, ns = table.span(base, n)
+    call("erd_sgd_momentum_groups", _p(p), _p(g), _p(buf), base, n, _p(table.table), s0, ns, table.offsets[s0],
+         table.offsets[s0 + ns], lr, momentum, grad_scale, _p(clip_coef),
+         1 if first_step else 0, _stream())
+
+
+def grad_sqnorm_into(g: Tensor, partials: Tensor) -> None:
+    """sum of squares of the fp32 range g as ERD_SQNORM_PARTS fp64 partials (one slot of the buffer clip_coef_ folds)"""
+    assert g.is_contiguous() and g.dtype == torch.float32 and g.numel() % 4 == 0
+    assert partials.is_contiguous() and partials.dtype == torch.float64 and partials.numel() == _lib.ERD_SQNORM_PARTS
+    call("erd_grad_sqnorm", _p(g), g.numel(), _p(partials), _stream())
+
+
+def clip_coef_(partials: Tensor, grad_scale: float, max_norm: float, out: Tensor) -> None:
+    """torch.nn.utils.clip_grad_norm_'s two numbers from the slots of grad_sqnorm_into, on the device:
+    out[0] = grad_scale * sqrt(sum), out[1] = min(1, max_norm / (out[0] + 1e-6))"""
+    assert partials.is_contiguous() and partials.dtype == torch.float64 and partials.numel() % _lib.ERD_SQNORM_PARTS == 0
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == 2
+    call("erd_clip_coef", _p(partials), partials.numel() // _lib.ERD_SQNORM_PARTS, grad_scale, max_norm, _p(out), _stream())
+
+
+def grad_accumulate_(acc: Tensor, g: Tensor, first: bool) -> None:
+    """acc = g (first micro-step of an accumulation window) or acc += g"""
+    assert acc.is_contiguous() and g.is_contiguous() and acc.numel() == g.numel() and acc.numel() % 4 == 0
+    call("erd_grad_accumulate", _p(acc), _p(g), acc.numel(), 1 if first else 0, _stream())
+
+
 # ---------------------------------------------------------------------------------------------
 # ERS / anchors / ATSS / losses
 # ---------------------------------------------------------------------------------------------

@@ -1,0 +1,135 @@
+"""The `optim_wrapper` options beside the optimizer itself, resolved on the host: `paramwise_cfg` -> one learning rate and
+one weight decay per parameter, `clip_grad` and `accumulative_counts` checked, the window rule of gradient accumulation, and
+the `param_groups` a checkpoint stores.  Pure Python: nothing here needs a GPU.
+
+`resolve_paramwise` restates mmengine's `DefaultOptimWrapperConstructor.add_params` (mmengine/optim/optimizer/
+default_constructor.py) from its documented rules; mmengine is not a dependency and the restatement is NOT pinned against it
+by a fixture ("unpinned").
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional
+
+import torch.nn as nn
+
+PARAMWISE_KEYS = ("custom_keys", "bias_lr_mult", "bias_decay_mult", "norm_decay_mult", "flat_decay_mult",
+                  "dwconv_decay_mult", "dcn_offset_lr_mult", "bypass_duplicate")
+CUSTOM_KEYS = ("lr_mult", "decay_mult")
+CLIP_KEYS = ("max_norm", "norm_type", "error_if_nonfinite")
+
+
+def _is_norm(m: nn.Module) -> bool:
+    from .modules import FrozenStatBN, GNHolder
+    return isinstance(m, (FrozenStatBN, GNHolder, nn.modules.batchnorm._BatchNorm, nn.GroupNorm, nn.LayerNorm))
+
+
+def check_paramwise(paramwise_cfg: Optional[dict]) -> dict:
+    cfg = dict(paramwise_cfg or {})
+    for k in cfg:
+        if k not in PARAMWISE_KEYS:
+            raise ValueError(f"paramwise_cfg: unknown key '{k}' (known: {', '.join(PARAMWISE_KEYS)})")
+    ck = cfg.get("custom_keys", {})
+    if not isinstance(ck, dict):
+        raise ValueError(f"paramwise_cfg: 'custom_keys' must be a dict, got {type(ck).__name__}")
+    for key, opts in ck.items():
+        if not isinstance(opts, dict):
+            raise ValueError(f"paramwise_cfg: custom_keys['{key}'] must be a dict, got {type(opts).__name__}")
+        for k in opts:
+            if k not in CUSTOM_KEYS:
+                raise ValueError(f"paramwise_cfg: unknown key '{k}' in custom_keys['{key}'] (known: {', '.join(CUSTOM_KEYS)})")
+    return cfg
+
+
+def resolve_paramwise(model: nn.Module, base_lr: float, base_wd: float, paramwise_cfg: Optional[dict]) -> List[dict]:
+    """-> one dict(name, lr_mult, lr, weight_decay, requires_grad) per parameter, in `model.parameters()` order.
+    Per parameter with full dotted name n, own name `name` and owning module m:
+      1. the keys of `custom_keys`, longest first and alphabetical among equal lengths; the first one that is a SUBSTRING of n
+         sets lr = base_lr * lr_mult and weight_decay = base_wd * decay_mult (both default 1) and ends the search;
+      2. otherwise lr = base_lr * bias_lr_mult for a `bias` that does not belong to a normalisation layer, and
+      3. weight_decay = base_wd * norm_decay_mult in a normalisation layer, else * bias_decay_mult for a `bias`, else
+         * flat_decay_mult for a 1-D parameter; a multiplier that is not given is passed over (mmengine's `elif` chain: the
+         bias of a normalisation layer takes bias_decay_mult when norm_decay_mult is absent);
+      4. dwconv_decay_mult, dcn_offset_lr_mult and bypass_duplicate have nothing to act on in these models (no depthwise or
+         deformable convolution, no shared parameter).
+    Frozen parameters keep the base values."""
+    cfg = check_paramwise(paramwise_cfg)
+    custom = cfg.get("custom_keys", {})
+    keys = sorted(sorted(custom.keys()), key=len, reverse=True)
+    bias_lr, bias_wd = cfg.get("bias_lr_mult"), cfg.get("bias_decay_mult")
+    norm_wd, flat_wd = cfg.get("norm_decay_mult"), cfg.get("flat_decay_mult")
+    by_id: Dict[int, dict] = {}
+    for prefix, m in model.named_modules():
+        norm = _is_norm(m)
+        for name, p in m.named_parameters(recurse=False):
+            if id(p) in by_id:
+                continue
+            n = f"{prefix}.{name}" if prefix else name
+            lr_mult, wd_mult = 1.0, 1.0
+            if p.requires_grad:
+                key = next((k for k in keys if k in n), None)
+                if key is not None:
+                    lr_mult = float(custom[key].get("lr_mult", 1.0))
+                    wd_mult = float(custom[key].get("decay_mult", 1.0))
+                else:
+                    if name == "bias" and not norm and bias_lr is not None:
+                        lr_mult = float(bias_lr)
+                    if norm and norm_wd is not None:
+                        wd_mult = float(norm_wd)
+                    elif name == "bias" and bias_wd is not None:
+                        wd_mult = float(bias_wd)
+                    elif p.dim() == 1 and flat_wd is not None:
+                        wd_mult = float(flat_wd)
+            by_id[id(p)] = dict(name=n, lr_mult=lr_mult, lr=base_lr * lr_mult, weight_decay=base_wd * wd_mult,
+                                requires_grad=bool(p.requires_grad))
+    return [by_id[id(p)] for p in model.parameters()]
+
+
+def check_clip_grad(clip_grad: Optional[dict]) -> Optional[dict]:
+    """-> dict(max_norm, error_if_nonfinite) or None.  Only the 2-norm is built."""
+    if clip_grad is None:
+        return None
+    cg = dict(clip_grad)
+    for k in cg:
+        if k not in CLIP_KEYS:
+            raise ValueError(f"clip_grad: unknown key '{k}' (known: {', '.join(CLIP_KEYS)})")
+    if "max_norm" not in cg:
+        raise ValueError("clip_grad: 'max_norm' is missing")
+    if float(cg.get("norm_type", 2)) != 2.0:
+        raise NotImplementedError(f"clip_grad: norm_type={cg['norm_type']} (only the 2-norm is built)")
+    if not float(cg["max_norm"]) > 0:
+        raise ValueError(f"clip_grad: max_norm={cg['max_norm']} must be positive")
+    return dict(max_norm=float(cg["max_norm"]), error_if_nonfinite=bool(cg.get("error_if_nonfinite", False)))
+
+
+def check_accumulative_counts(k) -> int:
+    if int(k) != k or int(k) < 1:
+        raise ValueError(f"accumulative_counts={k!r} must be a positive integer")
+    return int(k)
+
+
+def should_update(it: int, k: int) -> bool:
+    """mmengine's OptimWrapper.should_update by iteration: the call at 0-based iteration `it` applies the window"""
+    return (it + 1) % k == 0
+
+
+def accumulation_windows(iters: int, k: int) -> List[tuple]:
+    """(0-based iteration that triggers the update or None for the closing flush, micro-steps in the window) of a run of
+    `iters` iterations followed by a flush: the schedule ERDTrainer follows"""
+    out, m = [], 0
+    for it in range(iters):
+        m += 1
+        if should_update(it, k):
+            out.append((it, m))
+            m = 0
+    if m:
+        out.append((None, m))
+    return out
+
+
+def build_param_groups(resolved: List[dict], last_lr: float, base_lr: float, momentum: float) -> List[dict]:
+    """`param_groups` of the optimizer state dict under a paramwise_cfg, in torch.optim.SGD's layout: one group per parameter
+    in `model.parameters()` order (what mmengine's constructor builds), each with its own lr (the schedule's current factor
+    last_lr / base_lr applied), initial_lr and weight_decay"""
+    return [dict(lr=last_lr * r["lr_mult"], momentum=momentum, dampening=0, weight_decay=r["weight_decay"], nesterov=False,
+                 maximize=False, foreach=None, differentiable=False, initial_lr=base_lr * r["lr_mult"], params=[i])
+            for i, r in enumerate(resolved)]

@@ -229,10 +229,14 @@ class Runner:
         bs = int(cfg.train_dataloader.batch_size)
         self.schedule = ParamSchedule(cfg.get("param_scheduler"))
         asl = cfg.get("auto_scale_lr") or {}
+        # the wrapper's own keys (mmengine OptimWrapper / DefaultOptimWrapperConstructor); passed on only when the config sets them
+        ow = cfg.optim_wrapper
+        extra = {k: (ow[k].to_dict() if hasattr(ow[k], "to_dict") else ow[k])
+                 for k in ("paramwise_cfg", "clip_grad", "accumulative_counts") if ow.get(k) is not None}
         self.trainer = ERDTrainer(self.model, lr=opt.lr, momentum=opt.get("momentum", 0.0),
                                   weight_decay=opt.get("weight_decay", 0.0),
                                   base_batch_size=asl.get("base_batch_size", 16), batch_size_per_gpu=bs,
-                                  auto_scale_lr=bool(asl.get("enable", False)), warmup_iters=0)
+                                  auto_scale_lr=bool(asl.get("enable", False)), warmup_iters=0, **extra)
         self.trainer.lr_factor = self.schedule.iter_factor          # warm-up comes from the config's LinearLR
         # data parallel: CUs the whole-chip grids leave to RCCL's resident kernels.  The launcher does not PROBE (ERDTrainer.
         # tune_cu_reserve spends optimisation steps on one batch: bench.py does that and prints `collectives.cu_reserve`); it takes
@@ -290,6 +294,8 @@ class Runner:
                 window.append(logv)
                 done += 1
                 if (i + 1) % self.log_interval == 0 or (max_iters and done >= max_iters):
+                    if self.trainer.clip is not None:
+                        self.trainer.flush(close_window=False)    # the last step's update writes its grad_norm: queue it now
                     torch.cuda.synchronize()
                     keys = [k for k in window[0] if "loss" in k]
                     avg = {k: float(sum(float(w[k].detach()) for w in window) / len(window)) for k in keys}
@@ -299,6 +305,13 @@ class Runner:
                     if bad:
                         raise FloatingPointError(f"loss became infinite or NaN! ({', '.join(bad)} at epoch {self.epoch + 1}, "
                                                  f"iteration {i + 1})")
+                    # clip_grad: the norm of the (mean) gradient before clipping, averaged over the updates of the window
+                    norms = [float(w["grad_norm"]) for w in window if "grad_norm" in w]
+                    if norms:
+                        avg["grad_norm"] = sum(norms) / len(norms)
+                        if self.trainer.clip["error_if_nonfinite"] and not math.isfinite(avg["grad_norm"]):
+                            raise FloatingPointError(f"the gradient norm became infinite or NaN (epoch {self.epoch + 1}, "
+                                                     f"iteration {i + 1}; clip_grad.error_if_nonfinite)")
                     dt = (time.perf_counter() - t0) / (i + 1)
                     rec = dict(epoch=self.epoch + 1, iter=i + 1, lr=self.trainer.last_lr, time=dt, **avg)
                     self.history.append(rec)
@@ -308,6 +321,8 @@ class Runner:
                 if max_iters and done >= max_iters:
                     self.trainer.flush()
                     return self.history
+            if self.trainer.accum > 1:
+                self.trainer.flush()      # an accumulation window never spans an epoch end
             self.epoch += 1
             if self.rank == 0 and self.ckpt_interval > 0 and self.epoch % self.ckpt_interval == 0:
                 path = os.path.join(self.work_dir, f"epoch_{self.epoch}.pth")

@@ -354,6 +354,35 @@ int erd_level_scale_bwd(const float* x, const float* dy, const float* alphas, fl
 int erd_sgd_momentum(float* p, const float* g, float* buf, int64_t n, float lr, float momentum,
                      float weight_decay, float grad_scale, int first_step, erd_stream_t stream);
 
+/* ---- the optimizer wrapper's options (mmengine OptimWrapper: paramwise_cfg, clip_grad, accumulative_counts) -------- */
+/* One entry per parameter of the flat buffers, in layout order: the entry covers the elements from its `begin` up to the next
+ * entry's (the zero padding behind a parameter included).  Offsets are multiples of 4 floats, so no float4 straddles two. */
+typedef struct {
+    int64_t begin;       /* absolute element offset in the flat buffers */
+    float lr_mult;       /* learning rate of the segment = lr * lr_mult */
+    float weight_decay;  /* absolute (base weight decay * decay_mult) */
+} erd_sgd_seg;
+/* checks a host table (seg_off[nseg + 1] increasing multiples of 4, the last one the end of the buffers) and writes the
+ * nseg + 1 entries of its device form; synchronises the stream (once per trainer) */
+int erd_sgd_groups_table(const int64_t* seg_off, const float* lr_mult, const float* weight_decay, int nseg,
+                         erd_sgd_seg* table_dev, erd_stream_t stream);
+/* torch.optim.SGD with parameter groups: erd_sgd_momentum over the elements [base, base + n) of the flat buffers (p, g, buf
+ * point AT element `base`) with lr * lr_mult[s] and weight_decay[s] of the segments [seg0, seg0 + nseg) of the device table,
+ * which span [seg0_begin, seg_end) and must cover the range.  One launch however many segments.  clip_coef: device float that
+ * multiplies grad_scale, or null (= 1).  Multipliers 1 and one decay give the bits of erd_sgd_momentum. */
+int erd_sgd_momentum_groups(float* p, const float* g, float* buf, int64_t base, int64_t n, const erd_sgd_seg* table_dev,
+                            int seg0, int nseg, int64_t seg0_begin, int64_t seg_end, float lr, float momentum,
+                            float grad_scale, const float* clip_coef, int first_step, erd_stream_t stream);
+/* torch.nn.utils.clip_grad_norm_, norm_type 2, in two launches.  erd_grad_sqnorm: sum of squares of g[0, n) into a slot of
+ * ERD_SQNORM_PARTS fp64 partials (fixed partition, fp64 accumulation, no float atomics: bitwise reproducible).
+ * erd_clip_coef: folds `nslots` consecutive slots in a fixed order and writes out[0] = total_norm = grad_scale * sqrt(sum),
+ * out[1] = min(1, max_norm / (total_norm + 1e-6)) on the device. */
+#define ERD_SQNORM_PARTS 1024
+int erd_grad_sqnorm(const float* g, int64_t n, double* partials, erd_stream_t stream);
+int erd_clip_coef(const double* partials, int nslots, float grad_scale, float max_norm, float* out, erd_stream_t stream);
+/* accumulative_counts: acc[0, n) = g (first != 0) or acc += g, plain fp32 adds */
+int erd_grad_accumulate(float* acc, const float* g, int64_t n, int first, erd_stream_t stream);
+
 /* ---- ERS (gfl_increment_erd.py:143-163) -------------------------------------------------------- */
 /* per image: m_c = max_k sigmoid(cls[a,k]), keep iff m_c > mean + 2*std (unbiased); m_b = max_j
  * bbox[a,j] likewise.  Writes masks [N][A] (uint8), ascending index lists idx_*[N][A] (int64) and

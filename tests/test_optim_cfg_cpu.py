@@ -1,0 +1,165 @@
+"""CPU: the optim_wrapper options on the host (erd_amd/optim_cfg.py) -- paramwise_cfg resolved per parameter on the GFL-R50
+student of the 40+40 config, the accumulation window rule, the param_groups a checkpoint stores, the example config."""
+import os
+
+import pytest
+
+from erd_amd import Config, MODELS
+from erd_amd import optim_cfg as OC
+from e2e_util import CFG_INCRE, ROOT
+
+CFG_OPTIM = os.path.join(ROOT, "configs", "gfl_increment", "gfl_r50_fpn_1x_coco_first_40_incre_last_40_cats_optim.py")
+TABLE_CFG = dict(norm_decay_mult=0., bias_lr_mult=2., bias_decay_mult=0.,
+                 custom_keys={'backbone': dict(lr_mult=0.1), 'backbone.layer4': dict(lr_mult=0.5, decay_mult=2.)})
+# parameter -> (lr, weight decay) at base lr 0.01, base weight decay 1e-4
+TABLE = {
+    "backbone.layer4.0.conv1.weight": (0.005, 2e-4),
+    "backbone.layer2.0.bn1.weight": (0.001, 1e-4),               # the custom key wins over norm_decay_mult
+    "bbox_head.cls_convs.0.gn.weight": (0.01, 0.0),
+    "bbox_head.cls_convs.0.gn.bias": (0.01, 0.0),                # a normalisation layer's bias: no bias_lr_mult
+    "bbox_head.gfl_cls.bias": (0.02, 0.0),
+    "neck.lateral_convs.0.conv.bias": (0.02, 0.0),
+    "bbox_head.gfl_cls.weight": (0.01, 1e-4),
+}
+
+
+@pytest.fixture(scope="module")
+def student():
+    cfg = Config.fromfile(CFG_INCRE)
+    cfg.model.latest_model_flag = False
+    return MODELS.build(cfg.model)
+
+
+def _by_name(model, pw, lr=0.01, wd=1e-4):
+    rows = OC.resolve_paramwise(model, lr, wd, pw)
+    assert [r["name"] for r in rows] == [n for n, _ in model.named_parameters()]       # model.parameters() order
+    return {r["name"]: r for r in rows}
+
+
+def test_paramwise_cfg_resolves_to_the_known_answers(student):
+    got = _by_name(student, TABLE_CFG)
+    for name, (lr, wd) in TABLE.items():
+        assert got[name]["lr"] == pytest.approx(lr, rel=1e-12) and got[name]["weight_decay"] == pytest.approx(wd, rel=1e-12, abs=0), name
+        assert got[name]["lr_mult"] == pytest.approx(lr / 0.01, rel=1e-12)
+    # frozen parameters (stem, layer1) keep the base values whatever matches their name
+    frozen = [r for r in got.values() if not r["requires_grad"]]
+    assert frozen and all(r["name"].startswith("backbone.") and r["lr"] == 0.01 and r["weight_decay"] == 1e-4 for r in frozen)
+    # nothing given: every parameter at the base values
+    assert all(r["lr"] == 0.01 and r["weight_decay"] == 1e-4 and r["lr_mult"] == 1.0 for r in _by_name(student, {}).values())
+
+
+def test_custom_keys_match_substrings_longest_first_then_alphabetical(student):
+    got = _by_name(student, dict(custom_keys={'gn': dict(decay_mult=0.)}))
+    assert got["bbox_head.cls_convs.0.gn.weight"]["weight_decay"] == 0.0 and got["bbox_head.cls_convs.0.gn.weight"]["lr"] == 0.01
+    assert got["bbox_head.cls_convs.0.conv.weight"]["weight_decay"] == 1e-4
+    # two keys of EQUAL length that both match: 'conv1.' sorts before 'layer4' and wins
+    got = _by_name(student, dict(custom_keys={'layer4': dict(lr_mult=0.5), 'conv1.': dict(lr_mult=0.25)}))
+    assert got["backbone.layer4.0.conv1.weight"]["lr"] == pytest.approx(0.0025, rel=1e-12)
+    assert got["backbone.layer4.0.conv2.weight"]["lr"] == pytest.approx(0.005, rel=1e-12)
+    assert got["backbone.layer2.0.conv1.weight"]["lr"] == pytest.approx(0.0025, rel=1e-12)
+    # ... and the longer key wins whatever the alphabet says: 'layer4' (6 letters) before 'conv1' (5).  (The issue that asked for
+    # this resolver lists this pair as "equal lengths" with 0.0025 for the layer4 weight; by its own rule,
+    # sorted(sorted(keys), key=len, reverse=True), which is mmengine's, 'layer4' is tried first.)
+    got = _by_name(student, dict(custom_keys={'layer4': dict(lr_mult=0.5), 'conv1': dict(lr_mult=0.25)}))
+    assert got["backbone.layer4.0.conv1.weight"]["lr"] == pytest.approx(0.005, rel=1e-12)
+    assert got["backbone.layer2.0.conv1.weight"]["lr"] == pytest.approx(0.0025, rel=1e-12)
+    # flat_decay_mult reaches 1-D parameters that are neither in a normalisation layer nor a bias given a multiplier: here the
+    # biases (1-D) when bias_decay_mult is absent; the 0-d Scale parameters stay
+    got = _by_name(student, dict(flat_decay_mult=0.5))
+    assert got["bbox_head.gfl_cls.bias"]["weight_decay"] == pytest.approx(5e-5) and got["bbox_head.scales.0.scale"]["weight_decay"] == 1e-4
+    assert got["bbox_head.cls_convs.0.gn.weight"]["weight_decay"] == pytest.approx(5e-5)
+
+
+def test_unknown_keys_raise_value_errors_naming_the_key(student):
+    with pytest.raises(ValueError, match="bogus_mult"):
+        OC.resolve_paramwise(student, 0.01, 1e-4, dict(bogus_mult=1.0))
+    with pytest.raises(ValueError, match="custom_keys"):
+        OC.resolve_paramwise(student, 0.01, 1e-4, dict(custom_keys=[("backbone", dict(lr_mult=0.1))]))
+    with pytest.raises(ValueError, match="momentum_mult"):
+        OC.resolve_paramwise(student, 0.01, 1e-4, dict(custom_keys={"backbone": dict(momentum_mult=0.1)}))
+    with pytest.raises(ValueError, match="max_value"):
+        OC.check_clip_grad(dict(max_norm=35, max_value=1.0))
+    with pytest.raises(NotImplementedError):
+        OC.check_clip_grad(dict(max_norm=35, norm_type=1))
+    assert OC.check_clip_grad(None) is None
+    assert OC.check_clip_grad(dict(max_norm=35, norm_type=2)) == dict(max_norm=35.0, error_if_nonfinite=False)
+    # accepted, nothing to act on in this model
+    rows = OC.resolve_paramwise(student, 0.01, 1e-4, dict(dwconv_decay_mult=0., dcn_offset_lr_mult=0.1, bypass_duplicate=True))
+    assert all(r["lr"] == 0.01 and r["weight_decay"] == 1e-4 for r in rows)
+    for bad in (0, -1, 2.5):
+        with pytest.raises(ValueError):
+            OC.check_accumulative_counts(bad)
+
+
+def test_accumulation_window_rule():
+    """k = 3, 8 iterations: updates after iterations 3 and 6 (0-based 2 and 5), and the closing flush applies a window of 2"""
+    assert [it for it in range(8) if OC.should_update(it, 3)] == [2, 5]
+    assert OC.accumulation_windows(8, 3) == [(2, 3), (5, 3), (None, 2)]
+    assert OC.accumulation_windows(6, 3) == [(2, 3), (5, 3)]
+    assert OC.accumulation_windows(3, 1) == [(0, 1), (1, 1), (2, 1)]
+
+
+def test_param_groups_one_per_parameter_with_the_schedule_factor(student):
+    rows = OC.resolve_paramwise(student, 0.01, 1e-4, TABLE_CFG)
+    groups = OC.build_param_groups(rows, last_lr=0.01 * 0.1, base_lr=0.01, momentum=0.9)       # after a MultiStepLR decay
+    assert len(groups) == len(list(student.parameters())) and [g["params"] for g in groups] == [[i] for i in range(len(groups))]
+    names = [n for n, _ in student.named_parameters()]
+    for name, (lr, wd) in TABLE.items():
+        g = groups[names.index(name)]
+        assert g["initial_lr"] == pytest.approx(lr, rel=1e-12) and g["lr"] == pytest.approx(lr * 0.1, rel=1e-12)
+        assert g["weight_decay"] == pytest.approx(wd, rel=1e-12, abs=0) and g["momentum"] == 0.9 and g["nesterov"] is False
+    # the layout loads into a stock torch.optim.SGD over the same parameter list
+    import torch
+    ps = [torch.nn.Parameter(torch.zeros(1)) for _ in groups]
+    opt = torch.optim.SGD([dict(params=[p]) for p in ps], lr=0.01, momentum=0.9, weight_decay=1e-4)
+    opt.load_state_dict(dict(state={}, param_groups=groups))
+    assert opt.param_groups[names.index("bbox_head.gfl_cls.bias")]["lr"] == pytest.approx(0.002)
+
+
+def test_example_config_sets_the_three_keys():
+    cfg = Config.fromfile(CFG_OPTIM)
+    ow = cfg.optim_wrapper
+    assert ow.optimizer == dict(type="SGD", lr=0.01, momentum=0.9, weight_decay=0.0001) and ow.type == "OptimWrapper"
+    assert ow.paramwise_cfg.to_dict() == TABLE_CFG and ow.clip_grad == dict(max_norm=35, norm_type=2)
+    assert ow.accumulative_counts == 4
+    assert cfg.model.type == "GFLIncrementERD" and cfg.train_dataloader.dataset.ann_file.endswith("sel_last_40_cats.json")
+    from erd_amd.engine import ERDTrainer
+    import inspect
+    assert {"paramwise_cfg", "clip_grad", "accumulative_counts"} <= set(inspect.signature(ERDTrainer.__init__).parameters)
+
+
+def test_update_kernels_in_the_isa(tmp_path):
+    """what the compiler makes of the new kernels (hipcc cross-compiles without a GPU): no scratch; 16-byte loads and stores; the
+    element arithmetic of sgd_groups_kernel is sgd_kernel's (the same packed multiplies and fused multiply-adds: with multipliers
+    1 the two give the same bits, asserted on the GPU); the norm kernels accumulate in fp64 and use no atomics (bitwise
+    repeatable); the table search of sgd_groups_kernel runs on scalar loads."""
+    import re
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not installed")
+    out = tmp_path / "elementwise.s"
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function", "-S", "--cuda-device-only",
+                        "-o", str(out), "elementwise.hip"], cwd=os.path.join(ROOT, "erd_amd", "csrc"), capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    s = open(out).read()
+    bodies = {}
+    for m in re.finditer(r"^(_Z\S+):[^\n]*\n(.*?)^\s*\.end_amdhsa_kernel", s, re.S | re.M):
+        for k in ("sgd_kernel", "sgd_groups_kernel", "grad_sqnorm_kernel", "clip_coef_kernel", "grad_accumulate_kernel"):
+            if re.search(r"\d" + k + "E", m.group(1)):
+                bodies[k] = m.group(2)
+    assert len(bodies) == 5, sorted(bodies)
+    ops = lambda k, pat: len(re.findall(r"^\s*" + pat + r"\b", bodies[k], re.M))
+    for k, b in bodies.items():
+        assert ".amdhsa_private_segment_fixed_size 0" in b and "scratch_" not in b, k
+    for k in ("sgd_groups_kernel", "grad_sqnorm_kernel", "grad_accumulate_kernel"):
+        assert ops(k, "global_load_dwordx4") >= 1 and ops(k, "global_load_dword") == 0, k
+    assert ops("sgd_groups_kernel", "global_store_dwordx4") == 2 and ops("grad_accumulate_kernel", "global_store_dwordx4") >= 1
+    for pat in ("v_pk_mul_f32", "v_pk_fma_f32", "v_fma_f32", "v_add_f32", "v_pk_add_f32"):
+        assert ops("sgd_groups_kernel", pat) == ops("sgd_kernel", pat), pat
+    assert ops("sgd_kernel", "v_pk_fma_f32") == 6 and ops("sgd_kernel", "v_pk_mul_f32") == 2
+    assert ops("sgd_groups_kernel", "s_load_dwordx2") >= 1          # the per-tile binary search
+    for k in ("grad_sqnorm_kernel", "clip_coef_kernel"):
+        assert "atomic" not in bodies[k] and ops(k, "v_fma_f64") + ops(k, "v_add_f64") + ops(k, "v_mul_f64") >= 1, k

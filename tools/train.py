@@ -38,7 +38,9 @@ def main(argv=None):
     ap.add_argument("--amp", action="store_true")
     ap.add_argument("--auto-scale-lr", action="store_true")
     ap.add_argument("--resume", nargs="?", type=str, const="auto")
-    ap.add_argument("--cfg-options", nargs="+")
+    ap.add_argument("--cfg-options", nargs="+",
+                    help="KEY=VALUE overrides, e.g. optim_wrapper.accumulative_counts=4 \"optim_wrapper.clip_grad={'max_norm': 35}\" "
+                         "\"optim_wrapper.paramwise_cfg={'custom_keys': {'backbone': {'lr_mult': 0.1}}}\"")
     ap.add_argument("--launcher", choices=["none", "pytorch"], default="none")
     ap.add_argument("--synthetic", type=int, default=None, metavar="ITERS",
                     help="synthetic iterations per epoch instead of the config's COCO files (the default when they are absent)")
