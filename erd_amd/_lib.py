@@ -116,6 +116,7 @@ _SIGNATURES = {
     "erd_sgd_momentum": [P, P, P, i64, f32, f32, f32, f32, i32, P],
     "erd_sgd_groups_table": [P, P, P, i32, P, P],
     "erd_sgd_momentum_groups": [P, P, P, i64, i64, P, i32, i32, i64, i64, f32, f32, f32, P, i32, P],
+    "erd_adam_groups": [P, P, P, P, i64, i64, P, i32, i32, i64, i64, f32, f32, C.c_double, C.c_double, f32, f32, f32, f32, P, i32, P],
     "erd_grad_sqnorm": [P, i64, P, P],
     "erd_clip_coef": [P, i32, f32, f32, P, P],
     "erd_grad_accumulate": [P, P, i64, i32, P],

@@ -737,6 +737,60 @@ __global__ __launch_bounds__(256) void sgd_groups_kernel(float4* __restrict__ p,
     }
 }
 
+// torch.optim.AdamW (decoupled != 0) / torch.optim.Adam (decay joins the gradient) over the same flat buffers with the same segment
+// table, tile search and clip coefficient as sgd_groups_kernel; `seg` null: one learning rate lr0 and one decay wd0.  m / v: first and
+// second moment.  omb1 = 1 - beta1 and omb2 = 1 - beta2 are rounded from the host's doubles (1 - float(0.999) is 1.3e-5 off 0.001);
+// ib1 = 1 / (1 - beta1^t), isb2 = 1 / sqrt(1 - beta2^t).  28 B per element, no reuse: an HBM pass like the SGD one.  Divide and
+// square root are the compiler's correctly rounded ones, the fused multiply-adds are written out (the bits do not hang on what
+// the compiler contracts).  Zero padding stays zero (0 / (0 + eps)).
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float wd, float decay, float beta2,
+                                          float omb1, float omb2, float eps, float step, float isb2, int decoupled) {
+    if (decoupled) p *= decay; else g = fmaf(wd, p, g);
+    m = fmaf(g - m, omb1, m);
+    v = fmaf(beta2, v, (omb2 * g) * g);
+    p = fmaf(-step, m / fmaf(sqrtf(v), isb2, eps), p);
+}
+
+__global__ __launch_bounds__(256) void adam_groups_kernel(float4* __restrict__ p, const float4* __restrict__ g,
+                                                          float4* __restrict__ m, float4* __restrict__ v, int64_t n4, int64_t base,
+                                                          const erd_sgd_seg* __restrict__ seg, int nseg, float lr0, float wd0,
+                                                          float beta2, float omb1, float omb2, float eps, float ib1, float isb2,
+                                                          float gs0, const float* __restrict__ coef, int decoupled) {
+    const float gs = coef ? gs0 * coef[0] : gs0;
+    for (int64_t t0 = blockIdx.x * 256ll; t0 < n4; t0 += (int64_t)gridDim.x * 256) {
+        int lo = 0;
+        if (seg) {                               // last entry whose begin <= the tile's first element, as in sgd_groups_kernel
+            const int64_t e0 = base + t0 * 4;
+            int hi = nseg - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (seg[mid].begin <= e0) lo = mid; else hi = mid - 1;
+            }
+        }
+        const int64_t i = t0 + threadIdx.x;
+        if (i >= n4) continue;
+        float lr = lr0, wd = wd0;
+        if (seg) {
+            const int64_t e = base + i * 4;
+            int s = lo;
+            while (s + 1 < nseg && seg[s + 1].begin <= e) ++s;
+            lr = lr0 * seg[s].lr_mult;
+            wd = seg[s].weight_decay;
+        }
+        const float decay = 1.f - lr * wd, step = lr * ib1;
+        float4 pp = p[i], mm = m[i], vv = v[i];
+        float4 gg = g[i];
+        gg.x *= gs; gg.y *= gs; gg.z *= gs; gg.w *= gs;
+        adam_elem(pp.x, gg.x, mm.x, vv.x, wd, decay, beta2, omb1, omb2, eps, step, isb2, decoupled);
+        adam_elem(pp.y, gg.y, mm.y, vv.y, wd, decay, beta2, omb1, omb2, eps, step, isb2, decoupled);
+        adam_elem(pp.z, gg.z, mm.z, vv.z, wd, decay, beta2, omb1, omb2, eps, step, isb2, decoupled);
+        adam_elem(pp.w, gg.w, mm.w, vv.w, wd, decay, beta2, omb1, omb2, eps, step, isb2, decoupled);
+        m[i] = mm;
+        v[i] = vv;
+        p[i] = pp;
+    }
+}
+
 // sum of squares of g[0, n) as ERD_SQNORM_PARTS fp64 partials: workgroup b owns the float4 b*256 + t + k*PARTS*256 (a partition
 // that depends on n alone), every lane accumulates the exact fp64 squares of its elements in index order, the lanes fold through
 // the wave butterfly and the four waves in order.  No float atomics: the same gradient gives the same bits on every run.
@@ -1164,6 +1218,29 @@ extern "C" int erd_sgd_momentum_groups(float* p, const float* g, float* buf, int
                        reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(buf), n / 4, base,
                        table_dev + seg0, nseg, lr, momentum, grad_scale, clip_coef, first_step);
     return erd::check_launch("sgd_groups");
+}
+
+// torch.optim.AdamW / torch.optim.Adam (amsgrad=False, maximize=False) over [base, base + n) of the flat buffers, one launch: the
+// arguments of erd_sgd_momentum_groups with two moment buffers.  table_dev null: lr and weight_decay for every element (seg0, nseg,
+// seg0_begin, seg_end are not read); otherwise lr * lr_mult[s] and weight_decay[s] of the table (weight_decay is not read)
+extern "C" int erd_adam_groups(float* p, const float* g, float* exp_avg, float* exp_avg_sq, int64_t base, int64_t n,
+                               const erd_sgd_seg* table_dev, int seg0, int nseg, int64_t seg0_begin, int64_t seg_end, float lr,
+                               float weight_decay, double beta1, double beta2, float eps, float inv_bias1, float inv_sqrt_bias2,
+                               float grad_scale, const float* clip_coef, int decoupled, erd_stream_t stream) {
+    ERD_REQUIRE(((p && g && exp_avg && exp_avg_sq) || n == 0) && n % 4 == 0 && base % 4 == 0 && n >= 0 && base >= 0, "adam_groups: "
+                "bad args (base and n must be multiples of 4)");
+    ERD_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f, "adam_groups: betas (%g, %g) must lie in "
+                "[0, 1) and eps %g must not be negative", beta1, beta2, (double)eps);
+    ERD_REQUIRE(!table_dev || (seg0 >= 0 && nseg >= 1 && seg0_begin <= base && base + n <= seg_end), "adam_groups: segments [%lld, "
+                "%lld) do not cover the range [%lld, %lld)", (long long)seg0_begin, (long long)seg_end, (long long)base,
+                (long long)(base + n));
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(adam_groups_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(exp_avg),
+                       reinterpret_cast<float4*>(exp_avg_sq), n / 4, base, table_dev ? table_dev + seg0 : nullptr, nseg, lr,
+                       weight_decay, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, inv_bias1, inv_sqrt_bias2,
+                       grad_scale, clip_coef, decoupled);
+    return erd::check_launch("adam_groups");
 }
 
 // torch.nn.utils.clip_grad_norm_ (norm_type 2; the reference: OptimWrapper clip_grad), first half: the sum of squares of g[0, n) as

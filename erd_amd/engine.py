@@ -323,11 +323,20 @@ class ERDTrainer:
                  base_batch_size: int = 16, batch_size_per_gpu: Optional[int] = None, auto_scale_lr: bool = True,
                  warmup_iters: int = 500, warmup_start_factor: float = 0.001, bucket_mb: int = 32,
                  overlap_teacher: bool = True, teacher_graph: bool = False, step_graph: bool = False,
-                 paramwise_cfg: Optional[dict] = None, clip_grad: Optional[dict] = None, accumulative_counts: int = 1):
+                 paramwise_cfg: Optional[dict] = None, clip_grad: Optional[dict] = None, accumulative_counts: int = 1,
+                 optimizer: Optional[dict] = None):
         """paramwise_cfg / clip_grad / accumulative_counts: the `optim_wrapper` keys of those names (mmengine's OptimWrapper and
         DefaultOptimWrapperConstructor; optim_cfg.py).  Without them the update is ONE scalar learning rate and weight decay
-        (erd_sgd_momentum) exactly as before; with any of them see _update_bucket_ext / _apply_pending_ext."""
+        (erd_sgd_momentum) exactly as before; with any of them see _update_bucket_ext / _apply_pending_ext.
+        optimizer: `optim_wrapper.optimizer`.  None or type='SGD': the SGD update from `lr`, `momentum`, `weight_decay` above.
+        type='AdamW' / 'Adam' (optim_cfg.check_optimizer): lr, betas, eps and weight_decay come from THIS dict (torch's defaults
+        where it is silent) and every launch site of the SGD kernels launches erd_adam_groups instead -- same buckets, grad
+        scale, clip coefficient, accumulation window and derived-state refresh."""
         self.model = model
+        self.opt = OC.check_optimizer(optimizer)
+        self.adam = self.opt["type"] in OC.ADAM_TYPES
+        if self.adam:
+            lr, weight_decay = self.opt["lr"], self.opt["weight_decay"]
         self.clip = OC.check_clip_grad(clip_grad)
         self.accum = OC.check_accumulative_counts(accumulative_counts)
         if step_graph and self.accum > 1:
@@ -355,6 +364,12 @@ class ERDTrainer:
         self._pending_lr = self.base_lr
         self._first = True
         self._pending = False                # an un-applied gradient sits in flat.grad
+        # AdamW / Adam: the first moment lives in flat.momentum, the second in one more flat buffer (not allocated for SGD);
+        # `_t` counts the updates planned so far -- one per CLOSED window, not per micro-step -- and `_pending_t` is the count of
+        # the update being issued / pending, fixed with `_pending_lr` when the step is planned: every bucket of one step takes
+        # the same bias corrections although the update is deferred behind the next teacher forward
+        self.exp_avg_sq = torch.zeros_like(self.flat.momentum) if self.adam else None
+        self._t = self._pending_t = 0
         # optim_wrapper options.  `resolved`: per-parameter lr multiplier / weight decay (model.parameters() order); `_table`: its
         # device form, one segment per flat parameter (also built for clipping alone: the coefficient enters through the same
         # kernel); `_acc`: the accumulation window's gradient sum (backward kernels need flat.grad zero at the start of every
@@ -447,8 +462,11 @@ class ERDTrainer:
         if self._ext:
             return self._update_bucket_ext(b)
         s, e, _ = self.flat.buckets[b]
-        K.sgd_momentum_(self.flat.data[s:e], self.flat.grad[s:e], self.flat.momentum[s:e], self._pending_lr, self.momentum,
-                        self.weight_decay, 1.0 / self.world, self._first)
+        if self.adam:
+            self._adam_update(s, e, self.flat.grad, 1.0 / self.world)
+        else:
+            K.sgd_momentum_(self.flat.data[s:e], self.flat.grad[s:e], self.flat.momentum[s:e], self._pending_lr, self.momentum,
+                            self.weight_decay, 1.0 / self.world, self._first)
         self.flat.refresh_shadow(b)
         self.prefold.run_group(b)
         if self.prefold.valid[0]:
@@ -456,18 +474,32 @@ class ERDTrainer:
         else:
             self.prep.invalidate()
 
+    def _adam_update(self, s: int, e: int, g: Tensor, scale: float) -> None:
+        """AdamW / Adam on [s, e) of the flat buffers from the gradient buffer g, one launch: the learning rate and the update
+        count of the step as planned, the segment table and the clip coefficient when the trainer has them"""
+        K.adam_groups_(self.flat.data[s:e], g[s:e], self.flat.momentum[s:e], self.exp_avg_sq[s:e], s, self._table, self._pending_lr,
+                       self.weight_decay, self.opt["betas"], self.opt["eps"], self._pending_t, scale, self.opt["type"] == "AdamW",
+                       None if self.clip is None else self._norm_out[1:2])
+
+    def _count_update(self) -> None:
+        """one more update is planned (a window closes): AdamW's / Adam's `step`"""
+        self._t += 1
+        self._pending_t = self._t
+
     # -- the update with optim_wrapper options (paramwise_cfg, clip_grad, accumulative_counts) ------------------------------
     def _plan_step(self, log_vars) -> None:
         """fixes what the update of the step being issued does BEFORE its backward pass (per-bucket updates start inside it):
         first micro-step of a window or not, closing the window or not (mmengine: (iter + 1) % accumulative_counts == 0),
         micro-steps in the window; with clipping a closing step logs `grad_norm`, a device float written by the update"""
         if not self._ext:
+            self._count_update()
             return
         self._micro_first = self._window == 0
         self._window += 1
         self._close, self._m = OC.should_update(self.iter, self.accum), self._window
         if self._close:
             self._window = 0
+            self._count_update()
             if self.clip is not None:
                 log_vars["grad_norm"] = self._new_norm_out()[0]
 
@@ -484,7 +516,9 @@ class ERDTrainer:
         s, e = (0, self.flat.total) if b is None else self.flat.buckets[b][:2]
         g = self.flat.grad if self._acc is None else self._acc
         scale = 1.0 / (self.world * self._m)
-        if self._table is None:
+        if self.adam:
+            self._adam_update(s, e, g, scale)
+        elif self._table is None:
             K.sgd_momentum_(self.flat.data[s:e], g[s:e], self.flat.momentum[s:e], self._pending_lr, self.momentum,
                             self.weight_decay, scale, self._first)
         else:
@@ -554,8 +588,11 @@ class ERDTrainer:
             return
         if self.sync is not None:
             self.sync.wait()
-        K.sgd_momentum_(self.flat.data, self.flat.grad, self.flat.momentum, self._pending_lr, self.momentum,
-                        self.weight_decay, 1.0 / self.world, self._first)
+        if self.adam:
+            self._adam_update(0, self.flat.total, self.flat.grad, 1.0 / self.world)
+        else:
+            K.sgd_momentum_(self.flat.data, self.flat.grad, self.flat.momentum, self._pending_lr, self.momentum,
+                            self.weight_decay, 1.0 / self.world, self._first)
         self._first = False
         self._pending = False
         self.flat.refresh_shadow()
@@ -573,6 +610,7 @@ class ERDTrainer:
         self._apply_pending()
         if close_window and self._ext and self._window > 0:
             self._m, self._window = self._window, 0
+            self._count_update()
             if self.clip is not None:
                 self._new_norm_out()
             self._apply_window()
@@ -622,11 +660,22 @@ class ERDTrainer:
             if st is not None and st != cur:
                 cur.wait_stream(st)
 
-    # -- optimizer state in torch.optim.SGD's state_dict layout (what the reference's checkpoints hold) ---------
+    # -- optimizer state in torch.optim.SGD's state_dict layout (what the reference's checkpoints hold), or torch.optim.AdamW's ------
     def optimizer_state_dict(self) -> dict:
         self.flush()
         index = {id(p): i for i, p in enumerate(self.model.parameters())}
         state = {}
+        if self.adam:
+            if self._t > 0:                  # (empty before the first update, as torch's is)
+                for p, off in zip(self.flat.params, self.flat.offsets):
+                    m, v = _storage_view(self.flat.momentum, off, p), _storage_view(self.exp_avg_sq, off, p)
+                    state[index[id(p)]] = dict(step=torch.tensor(float(self._t)), exp_avg=m.detach().cpu().contiguous().clone(),
+                                               exp_avg_sq=v.detach().cpu().contiguous().clone())
+            if self.resolved is not None:
+                return dict(state=state, param_groups=OC.build_param_groups(self.resolved, self.last_lr, self.base_lr, self.momentum,
+                                                                            optimizer=self.opt))
+            return dict(state=state, param_groups=[OC.adam_param_group(self.opt, self.last_lr, self.base_lr, self.weight_decay,
+                                                                       list(range(len(index))))])
         if not self._first:
             for p, off in zip(self.flat.params, self.flat.offsets):
                 buf = _storage_view(self.flat.momentum, off, p)
@@ -638,11 +687,38 @@ class ERDTrainer:
                      params=list(range(len(index))))
         return dict(state=state, param_groups=[group])
 
+    def _check_state_kind(self, sd: dict) -> None:
+        """state of the other optimizer kind is refused, not dropped: SGD's holds `momentum_buffer` (groups: `momentum`), AdamW's
+        and Adam's `exp_avg` (groups: `betas`)"""
+        entries = list(sd.get("state", {}).values()) + list(sd.get("param_groups", []))
+        found = ("AdamW/Adam" if any("exp_avg" in e or "betas" in e for e in entries) else
+                 "SGD" if any("momentum_buffer" in e or "momentum" in e for e in entries) else None)
+        mine = "AdamW/Adam" if self.adam else "SGD"
+        if found is not None and found != mine:
+            raise ValueError(f"the optimizer state is {found}'s and this trainer runs {self.opt['type']}: the state of one kind does "
+                             f"not load into the other (resume with the optimizer the checkpoint was written with)")
+
     def load_optimizer_state_dict(self, sd: dict) -> None:
         self.flush()
+        self._check_state_kind(sd)
         params = list(self.model.parameters())
         slot = {id(p): (p, off) for p, off in zip(self.flat.params, self.flat.offsets)}
         loaded = 0
+        if self.adam:
+            mine = [(params[int(i)], st) for i, st in sd.get("state", {}).items()
+                    if id(params[int(i)]) in slot and st.get("exp_avg") is not None and st.get("exp_avg_sq") is not None]
+            steps = {float(st["step"]) for _, st in mine}
+            if len(steps) > 1:
+                raise ValueError(f"the optimizer state holds different `step` values ({sorted(steps)}): the flat update keeps one "
+                                 f"count for all parameters")
+            for p, st in mine:
+                p, off = slot[id(p)]
+                _storage_view(self.flat.momentum, off, p).copy_(st["exp_avg"].to(self.device))
+                _storage_view(self.exp_avg_sq, off, p).copy_(st["exp_avg_sq"].to(self.device))
+                loaded += 1
+            self._t = self._pending_t = int(steps.pop()) if steps else 0
+            self._first = loaded == 0
+            return
         for i, st in sd.get("state", {}).items():
             p = params[int(i)]
             if id(p) not in slot or "momentum_buffer" not in st or st["momentum_buffer"] is None:

@@ -1309,6 +1309,28 @@ def sgd_momentum_groups_(p: Tensor, g: Tensor, buf: Tensor, base: int, table: Sg
          1 if first_step else 0, _stream())
 
 
+def adam_groups_(p: Tensor, g: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, base: int, table: Optional[SgdSegTable], lr: float,
+                 weight_decay: float, betas, eps: float, step: int, grad_scale: float, decoupled: bool,
+                 clip_coef: Optional[Tensor] = None) -> None:
+    """torch.optim.AdamW (decoupled) / torch.optim.Adam on the slices p, g, exp_avg, exp_avg_sq = flat[base:base + n], one launch.
+    `step`: the 1-based count of this update (the bias corrections are host doubles, optim_cfg.adam_bias_corrections); `table`
+    None: `lr` and `weight_decay` for every element, otherwise lr * multiplier and the decay of each segment; clip_coef as in
+    sgd_momentum_groups_"""
+    from .optim_cfg import adam_bias_corrections
+    assert p.is_contiguous() and g.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous()
+    assert p.numel() == g.numel() == exp_avg.numel() == exp_avg_sq.numel()
+    assert clip_coef is None or (clip_coef.dtype == torch.float32 and clip_coef.numel() == 1 and clip_coef.device == p.device)
+    n = p.numel()
+    s0, ns, b0, b1 = 0, 0, 0, 0
+    if table is not None:
+        s0, ns = table.span(base, n)
+        b0, b1 = table.offsets[s0], table.offsets[s0 + ns]
+    inv_bias1, inv_sqrt_bias2 = adam_bias_corrections(betas[0], betas[1], step)
+    call("erd_adam_groups", _p(p), _p(g), _p(exp_avg), _p(exp_avg_sq), base, n, None if table is None else _p(table.table), s0, ns,
+         b0, b1, lr, weight_decay, float(betas[0]), float(betas[1]), eps, inv_bias1, inv_sqrt_bias2, grad_scale, _p(clip_coef),
+         1 if decoupled else 0, _stream())
+
+
 def grad_sqnorm_into(g: Tensor, partials: Tensor) -> None:
     """sum of squares of the fp32 range g as ERD_SQNORM_PARTS fp64 partials (one slot of the buffer clip_coef_ folds)"""
     assert g.is_contiguous() and g.dtype == torch.float32 and g.numel() % 4 == 0

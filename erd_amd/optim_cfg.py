@@ -1,6 +1,7 @@
 """The `optim_wrapper` options beside the optimizer itself, resolved on the host: `paramwise_cfg` -> one learning rate and
 one weight decay per parameter, `clip_grad` and `accumulative_counts` checked, the window rule of gradient accumulation, and
-the `param_groups` a checkpoint stores.  Pure Python: nothing here needs a GPU.
+the `param_groups` a checkpoint stores; and the optimizer's own dict (`check_optimizer`: SGD, AdamW, Adam).  Pure Python:
+nothing here needs a GPU.
 
 `resolve_paramwise` restates mmengine's `DefaultOptimWrapperConstructor.add_params` (mmengine/optim/optimizer/
 default_constructor.py) from its documented rules; mmengine is not a dependency and the restatement is NOT pinned against it
@@ -126,10 +127,66 @@ def accumulation_windows(iters: int, k: int) -> List[tuple]:
     return out
 
 
-def build_param_groups(resolved: List[dict], last_lr: float, base_lr: float, momentum: float) -> List[dict]:
+def build_param_groups(resolved: List[dict], last_lr: float, base_lr: float, momentum: float,
+                       optimizer: Optional[dict] = None) -> List[dict]:
     """`param_groups` of the optimizer state dict under a paramwise_cfg, in torch.optim.SGD's layout: one group per parameter
     in `model.parameters()` order (what mmengine's constructor builds), each with its own lr (the schedule's current factor
-    last_lr / base_lr applied), initial_lr and weight_decay"""
+    last_lr / base_lr applied), initial_lr and weight_decay.  `optimizer`: a checked AdamW / Adam dict (check_optimizer) gives
+    that optimizer's layout instead (`momentum` is not read)"""
+    if optimizer is not None and optimizer["type"] in ADAM_TYPES:
+        return [adam_param_group(optimizer, last_lr * r["lr_mult"], base_lr * r["lr_mult"], r["weight_decay"], [i])
+                for i, r in enumerate(resolved)]
     return [dict(lr=last_lr * r["lr_mult"], momentum=momentum, dampening=0, weight_decay=r["weight_decay"], nesterov=False,
                  maximize=False, foreach=None, differentiable=False, initial_lr=base_lr * r["lr_mult"], params=[i])
             for i, r in enumerate(resolved)]
+
+
+# ---- the optimizer itself: SGD (the update the ERD configs use), AdamW, Adam ---------------------------------------------------
+ADAM_TYPES = ("AdamW", "Adam")
+ADAM_KEYS = ("type", "lr", "betas", "eps", "weight_decay", "amsgrad", "maximize")
+
+
+def check_optimizer(cfg: Optional[dict]) -> dict:
+    """`optim_wrapper.optimizer` -> a plain dict.  SGD (and None, the trainer's default) passes as it is: the trainer reads lr,
+    momentum and weight_decay from it as before.  AdamW / Adam -> dict(type, lr, betas, eps, weight_decay) with torch's defaults
+    filled in (weight_decay 0.01 decoupled for AdamW, 0 coupled for Adam)."""
+    if cfg is None:
+        return dict(type="SGD")
+    cfg = dict(cfg.to_dict() if hasattr(cfg, "to_dict") else cfg)
+    kind = cfg.get("type")
+    if kind == "SGD":
+        return cfg
+    if kind not in ADAM_TYPES:
+        raise NotImplementedError(f"optimizer: type={kind!r} is not built (built: SGD, {', '.join(ADAM_TYPES)})")
+    for k in cfg:
+        if k not in ADAM_KEYS:
+            raise ValueError(f"optimizer: unknown key '{k}' for {kind} (known: {', '.join(ADAM_KEYS)})")
+    for k in ("amsgrad", "maximize"):
+        if cfg.get(k):
+            raise NotImplementedError(f"optimizer: {k}=True is not built")
+    betas = cfg.get("betas", (0.9, 0.999))
+    if not isinstance(betas, (tuple, list)) or len(betas) != 2:
+        raise ValueError(f"optimizer: betas={betas!r} must be a pair")
+    betas = (float(betas[0]), float(betas[1]))
+    if not all(0.0 <= b < 1.0 for b in betas):
+        raise ValueError(f"optimizer: betas={betas} must lie in [0, 1)")
+    lr, eps = float(cfg.get("lr", 1e-3)), float(cfg.get("eps", 1e-8))
+    wd = float(cfg.get("weight_decay", 0.01 if kind == "AdamW" else 0.0))
+    if lr < 0 or eps < 0 or wd < 0:
+        raise ValueError(f"optimizer: lr={lr}, eps={eps} and weight_decay={wd} must not be negative")
+    return dict(type=kind, lr=lr, betas=betas, eps=eps, weight_decay=wd)
+
+
+def adam_bias_corrections(beta1: float, beta2: float, step: int) -> tuple:
+    """(1 / (1 - beta1^t), 1 / sqrt(1 - beta2^t)) of the t-th update (t >= 1) in double: what torch.optim.Adam divides the step size
+    and the root of the second moment by"""
+    if int(step) < 1:
+        raise ValueError(f"adam_bias_corrections: step={step!r} (updates count from 1)")
+    return 1.0 / (1.0 - float(beta1) ** int(step)), 1.0 / (1.0 - float(beta2) ** int(step)) ** 0.5
+
+
+def adam_param_group(optimizer: dict, lr: float, initial_lr: float, weight_decay: float, params: List[int]) -> dict:
+    """one entry of `param_groups` in torch.optim.AdamW's / Adam's layout"""
+    return dict(lr=lr, betas=tuple(optimizer["betas"]), eps=optimizer["eps"], weight_decay=weight_decay, amsgrad=False,
+                maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
+                decoupled_weight_decay=optimizer["type"] == "AdamW", initial_lr=initial_lr, params=list(params))

@@ -21,13 +21,14 @@ import torch.distributed as dist
 
 from .config import Config
 from .engine import ERDTrainer
+from .optim_cfg import check_optimizer
 from .registry import MODELS
 from .structures import DetDataSample, InstanceData
 from .validation import val_due
 
 
 # ---------------------------------------------------------------------------------------------------------
-# checkpoints: {'meta': ..., 'state_dict': OIHW fp32 tensors keyed as the reference's, 'optimizer': torch-SGD layout}
+# checkpoints: {'meta': ..., 'state_dict': OIHW fp32 tensors keyed as the reference's, 'optimizer': torch-SGD (or AdamW / Adam) layout}
 # ---------------------------------------------------------------------------------------------------------
 def model_state_dict(model: torch.nn.Module, with_teacher: bool = True) -> "OrderedDict[str, torch.Tensor]":
     """CPU copy of the state dict in the reference's layout (dense OIHW).  ``with_teacher=False`` drops the frozen
@@ -222,8 +223,7 @@ class Runner:
             model.init_weights()      # backbone.init_cfg 'Pretrained' (a loaded checkpoint supersedes it); raises when unresolvable
         self.model = model.to(self.device).train()
         opt = cfg.optim_wrapper.optimizer
-        if opt.type != "SGD":
-            raise NotImplementedError("only SGD (the ERD configs) is built")
+        checked = check_optimizer(opt)       # SGD, AdamW or Adam; anything else raises
         if cfg.optim_wrapper.get("type", "OptimWrapper") != "OptimWrapper":
             raise NotImplementedError("AMP is not built: the path computes in fp32")
         bs = int(cfg.train_dataloader.batch_size)
@@ -233,7 +233,9 @@ class Runner:
         ow = cfg.optim_wrapper
         extra = {k: (ow[k].to_dict() if hasattr(ow[k], "to_dict") else ow[k])
                  for k in ("paramwise_cfg", "clip_grad", "accumulative_counts") if ow.get(k) is not None}
-        self.trainer = ERDTrainer(self.model, lr=opt.lr, momentum=opt.get("momentum", 0.0),
+        if checked["type"] != "SGD":
+            extra["optimizer"] = checked
+        self.trainer = ERDTrainer(self.model, lr=opt.lr if checked["type"] == "SGD" else checked["lr"], momentum=opt.get("momentum", 0.0),
                                   weight_decay=opt.get("weight_decay", 0.0),
                                   base_batch_size=asl.get("base_batch_size", 16), batch_size_per_gpu=bs,
                                   auto_scale_lr=bool(asl.get("enable", False)), warmup_iters=0, **extra)

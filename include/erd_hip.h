@@ -373,6 +373,20 @@ int erd_sgd_groups_table(const int64_t* seg_off, const float* lr_mult, const flo
 int erd_sgd_momentum_groups(float* p, const float* g, float* buf, int64_t base, int64_t n, const erd_sgd_seg* table_dev,
                             int seg0, int nseg, int64_t seg0_begin, int64_t seg_end, float lr, float momentum,
                             float grad_scale, const float* clip_coef, int first_step, erd_stream_t stream);
+/* torch.optim.AdamW (decoupled != 0: p *= 1 - lr * wd) or torch.optim.Adam (decoupled == 0: g += wd * p), amsgrad=False,
+ * maximize=False, over the elements [base, base + n) of the flat buffers, one launch, with the range, table and clip_coef
+ * arguments of erd_sgd_momentum_groups.  Per element, g' = g * grad_scale * clip_coef:
+ *   exp_avg += (g' - exp_avg) * (1 - beta1);  exp_avg_sq = beta2 * exp_avg_sq + (1 - beta2) * g' * g';
+ *   p -= lr * inv_bias1 * exp_avg / (sqrt(exp_avg_sq) * inv_sqrt_bias2 + eps)
+ * with inv_bias1 = 1 / (1 - beta1^t), inv_sqrt_bias2 = 1 / sqrt(1 - beta2^t) of the update count t (host values).  The betas
+ * travel as doubles: 1 - beta is rounded to fp32 once, from the double (1 - float(0.999) is 1.3e-5 off 0.001).  table_dev null:
+ * `lr` and `weight_decay` hold for every element and seg0, nseg, seg0_begin, seg_end are not read; otherwise lr * lr_mult[s]
+ * and weight_decay[s] of the table's segments and `weight_decay` is not read.  Unit multipliers and one decay give the bits of
+ * the null table. */
+int erd_adam_groups(float* p, const float* g, float* exp_avg, float* exp_avg_sq, int64_t base, int64_t n,
+                    const erd_sgd_seg* table_dev, int seg0, int nseg, int64_t seg0_begin, int64_t seg_end, float lr,
+                    float weight_decay, double beta1, double beta2, float eps, float inv_bias1, float inv_sqrt_bias2,
+                    float grad_scale, const float* clip_coef, int decoupled, erd_stream_t stream);
 /* torch.nn.utils.clip_grad_norm_, norm_type 2, in two launches.  erd_grad_sqnorm: sum of squares of g[0, n) into a slot of
  * ERD_SQNORM_PARTS fp64 partials (fixed partition, fp64 accumulation, no float atomics: bitwise reproducible).
  * erd_clip_coef: folds `nslots` consecutive slots in a fixed order and writes out[0] = total_norm = grad_scale * sqrt(sum),
