@@ -1311,8 +1311,14 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
     constexpr int A_PL = BMR * A_ROWB, B_PL = BNR * B_ROWB;    // bytes per plane
     constexpr int BUF = 3 * (A_PL + B_PL);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* offa = reinterpret_cast<int*>(smem + 2 * BUF);        // [2][BK]
-    int* offb = offa + 2 * BK;                                 // [2][BX]
+    // Offset tables: FINAL byte offsets of a slice's pixels (the loading thread adds its constant channel term), TAB_INV for a pixel
+    // that does not exist (padding, past the end) -- with the channel term added it stays past the extent of any buffer we build
+    // (extents are below 2^31 bytes, erd_conv_wgrad).  A thread reads its four entries as ONE 16-byte LDS load, so a slot of the x
+    // table is padded to whole groups of four (three taps: 18 -> 20 entries).  A ring of 8 slots, filled four slices per pass.
+    constexpr int TB = (BX + 3) / 4 * 4, NSLOT = 8;
+    constexpr unsigned TAB_INV = 0x80000000u;
+    unsigned* offa = reinterpret_cast<unsigned*>(smem + 2 * BUF);      // [NSLOT][BK]
+    unsigned* offb = offa + NSLOT * BK;                                // [NSLOT][TB]
 
     const int tid = threadIdx.x;
     const int nci = (p.Cin + BNR - 1) / BNR, nco = (p.Cout + BMR - 1) / BMR;
@@ -1330,61 +1336,109 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
     const int kt_begin = bz * per;
     const int kt_end = min(nslices, kt_begin + per);
 
-    int P = 0;                                                 // (generic form: pixels of all maps)
-    if (!ROW3)
+    const int wave = tid >> 6, lane = tid & 63;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // (the compiler cannot see that tid >> 6 is the same in all lanes)
+
+    // ---- the table of FOUR slices per pass, by one wave (16 lanes per slice).  A map row is a run of UNITS -- one tap: its GW pixels,
+    // a slice being 16 consecutive units of the concatenated pixel axis; three taps: its ceil(GW / 16) row chunks, a slice being one
+    // unit -- and rows, images and segments follow each other without gaps.  The position (segment sl, image sn, row sa, unit sb) of a
+    // pass's first unit is wave-uniform: decoded once (the only integer divisions of the launch), then stepped by the units of a pass on
+    // the scalar side, with the segment's fields as scalar loads.  A lane walks from there by row wraps; a lane whose unit lies past the
+    // image of the first one (a pass that straddles an image or segment boundary, or the end of the axis) and, with one tap, every lane
+    // of a map narrower than 16 pixels (many wraps) decodes its unit index itself.
+    constexpr int UPS = ROW3 ? 1 : BK;                         // units per slice
+    auto row_units = [&](const erd_wgrad_seg& g) { return ROW3 ? (g.GW + BK - 1) / BK : g.GW; };
+    int P = nslices, sl = 0, sn = 0, sa = 0, sb = 0;         // P: units of all maps
+    if (!ROW3) {
+        P = 0;
         for (int l = 0; l < p.nseg; ++l) P += p.seg[l].N * p.seg[l].GH * p.seg[l].GW;
-    auto compute_offsets = [&](int kt, int slot) {
-        if (!ROW3) {
-            if (tid < BK) {
-                int pp = kt * BK + tid, oa = -1, ob = -1;
-                if (pp < P && kt < kt_end) {
+    }
+    {
+        int q = kt_begin * UPS;
+        for (; sl < p.nseg; ++sl) {
+            const int pl = p.seg[sl].N * p.seg[sl].GH * row_units(p.seg[sl]);
+            if (q < pl) break;
+            q -= pl;
+        }
+        if (sl < p.nseg) {
+            const int U = row_units(p.seg[sl]), GHU = p.seg[sl].GH * U;
+            sn = q / GHU;
+            q -= sn * GHU;
+            sa = q / U;
+            sb = q - sa * U;
+        }
+    }
+    // offsets of unit b of row a of image n of map g: dz pixel `oa` and x entry `ob` of the lane (three taps: entry e is column
+    // 16 b + e - 1 of row a + ky - 1; lanes e < 4 also have entry 16 + e, of which 18 and 19 pad the slot)
+    auto unit_offsets = [&](const erd_wgrad_seg& g, int n, int a, int b, unsigned& oa, unsigned& ob, unsigned& ob2) {
+        if constexpr (ROW3) {
+            const int e = lane & 15, zcol = b * BK + e, ih = a + ky - 1;
+            if (zcol < g.GW) oa = (unsigned)((int)(g.dz_off + n * g.dz_nstride) + (a * g.OW + zcol) * p.Cout) * 4u;
+            if ((unsigned)ih < (unsigned)g.IH) {
+                const int rowb = (int)(g.x_off + n * g.x_nstride) + ih * g.IW * p.Cin;
+                if ((unsigned)(zcol - 1) < (unsigned)g.IW) ob = (unsigned)(rowb + (zcol - 1) * p.Cin) * 4u;
+                if (e < 2 && zcol + 15 < g.IW) ob2 = (unsigned)(rowb + (zcol + 15) * p.Cin) * 4u;
+            }
+        } else {
+            oa = (unsigned)((int)(g.dz_off + n * g.dz_nstride) + ((a * p.out_stride + p.oy) * g.OW + (b * p.out_stride + p.ox)) * p.Cout) * 4u;
+            const int ih = a * p.in_stride + p.dy[ky], iw = b * p.in_stride + p.dx[ky];
+            if ((unsigned)ih < (unsigned)g.IH && (unsigned)iw < (unsigned)g.IW)
+                ob = (unsigned)((int)(g.x_off + n * g.x_nstride) + (ih * g.IW + iw) * p.Cin) * 4u;
+        }
+    };
+    auto walker_scalar = [&]() {         // (keeps the position in scalar registers, whatever the compiler made of the paths that lead here)
+        sl = __builtin_amdgcn_readfirstlane(sl);
+        sn = __builtin_amdgcn_readfirstlane(sn);
+        sa = __builtin_amdgcn_readfirstlane(sa);
+        sb = __builtin_amdgcn_readfirstlane(sb);
+    };
+    auto table_pass = [&](int ks) {      // slices ks .. ks + 3 (first unit at the walker's position) by the lanes of ONE wave
+        unsigned oa = TAB_INV, ob = TAB_INV, ob2 = TAB_INV;
+        const int u = ROW3 ? lane >> 4 : lane;          // the lane's unit, counted from the walker
+        if (sl < p.nseg) {
+            const erd_wgrad_seg& g = p.seg[sl];
+            const int U = row_units(g);
+            int a = sa, b = sb + u;
+            bool walked = ROW3 || g.GW >= BK;
+            if (walked) {
+                while (b >= U) { b -= U; ++a; }
+                walked = a < g.GH;
+            }
+            if (walked) unit_offsets(g, sn, a, b, oa, ob, ob2);
+            else {
+                int pp = ks * UPS + u;
+                if (pp < P) {
                     int l = 0;
 #pragma unroll 1
                     for (; l < p.nseg - 1; ++l) {
-                        const int pl = p.seg[l].N * p.seg[l].GH * p.seg[l].GW;
+                        const int pl = p.seg[l].N * p.seg[l].GH * row_units(p.seg[l]);
                         if (pp < pl) break;
                         pp -= pl;
                     }
-                    const erd_wgrad_seg& g = p.seg[l];
-                    const int GHW = g.GH * g.GW;
-                    const int n = pp / GHW;
-                    const int rem = pp - n * GHW;
-                    const int a = rem / g.GW;
-                    const int b = rem - a * g.GW;
-                    oa = (int)(g.dz_off + n * g.dz_nstride) + ((a * p.out_stride + p.oy) * g.OW + (b * p.out_stride + p.ox)) * p.Cout;
-                    const int ih = a * p.in_stride + p.dy[ky], iw = b * p.in_stride + p.dx[ky];
-                    if ((unsigned)ih < (unsigned)g.IH && (unsigned)iw < (unsigned)g.IW)
-                        ob = (int)(g.x_off + n * g.x_nstride) + (ih * g.IW + iw) * p.Cin;
+                    const erd_wgrad_seg& gl = p.seg[l];
+                    const int Ul = row_units(gl), GHU = gl.GH * Ul;
+                    const int n = pp / GHU;
+                    const int rem = pp - n * GHU;
+                    const int al = rem / Ul;
+                    unit_offsets(gl, n, al, rem - al * Ul, oa, ob, ob2);
                 }
-                offa[slot * BK + tid] = oa;
-                offb[slot * BX + tid] = ob;
             }
-            return;
         }
-        if (tid < BX) {
-            int oa = -1, ob = -1;
-            if (kt < kt_end) {
-                int l = 0, q = kt;
-#pragma unroll 1
-                for (; l < p.nseg - 1; ++l) {
-                    const int cnt = p.seg[l].N * p.seg[l].GH * ((p.seg[l].GW + BK - 1) / BK);
-                    if (q < cnt) break;
-                    q -= cnt;
-                }
-                const erd_wgrad_seg& g = p.seg[l];
-                const int cpr = (g.GW + BK - 1) / BK;
-                const int c = q % cpr;
-                const int rowi = q / cpr;
-                const int a = rowi % g.GH, n = rowi / g.GH;
-                const int bcol = c * BK + tid - 1;
-                const int ih = a + ky - 1;
-                if ((unsigned)bcol < (unsigned)g.IW && (unsigned)ih < (unsigned)g.IH)
-                    ob = (int)(g.x_off + n * g.x_nstride) + (ih * g.IW + bcol) * p.Cin;
-                const int zcol = c * BK + tid;
-                if (tid < BK && zcol < g.GW) oa = (int)(g.dz_off + n * g.dz_nstride) + (a * g.OW + zcol) * p.Cout;
-            }
-            if (tid < BK) offa[slot * BK + tid] = oa;
-            offb[slot * BX + tid] = ob;
+        const int slot = ((ks - kt_begin) & (NSLOT - 1)) + (lane >> 4), e = lane & 15;      // (ks - kt_begin is a multiple of 4)
+        offa[slot * BK + e] = oa;
+        offb[slot * TB + e] = ob;
+        if (ROW3 && e < 4) offb[slot * TB + BK + e] = ob2;
+    };
+    auto table_step = [&]() {            // the walker moves on by the units of a pass (scalar; every wave keeps its own copy)
+        walker_scalar();
+        sb += 4 * UPS;
+        while (sl < p.nseg && sb >= row_units(p.seg[sl])) {       // one row on; a row is never split between images or segments
+            sb -= row_units(p.seg[sl]);
+            const bool img = sa + 1 == p.seg[sl].GH;
+            sa = img ? 0 : sa + 1;
+            const bool seg = img && sn + 1 == p.seg[sl].N;
+            sn = seg ? 0 : sn + (img ? 1 : 0);
+            sl += seg ? 1 : 0;
         }
     };
 
@@ -1413,15 +1467,19 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
     static_assert(NA % 64 == 0, "staging roles are wave-uniform");
     const bool a_wave = __builtin_amdgcn_readfirstlane(is_a ? 1 : 0) != 0;
     const __amdgpu_buffer_rsrc_t rs_mine = a_wave ? rs_dz : rs_x;
-    float4 rv[4];
+    // requests: the thread's four table entries in one LDS read, one add each, four unconditional loads.  A thread whose channels lie
+    // past the end takes no part (its registers keep the zeros they start with)
+    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+    const bool ld_on = (is_a || is_b) && cok;
+    const unsigned col4 = (unsigned)col * 4u;
+    const unsigned* tab_mine = a_wave ? offa + pg * 4 : offb + pg * 4;
+    const int tab_slot = a_wave ? BK : TB;
+    float4 rv[4] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
     auto load_global = [&](int slot) {
-        if (is_a || is_b) {
+        if (ld_on) {
+            const u4v o = *reinterpret_cast<const u4v*>(tab_mine + slot * tab_slot);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int e = pg * 4 + i;
-                const int o = is_a ? offa[slot * BK + e] : (e < BX ? offb[slot * BX + e] : -1);
-                rv[i] = buf_load16(rs_mine, (o >= 0 && cok) ? (unsigned)(o + col) * 4u : OOB);
-            }
+            for (int i = 0; i < 4; ++i) rv[i] = buf_load16(rs_mine, o[i] + col4);
         }
     };
     auto store_lds = [&](int buf) {
@@ -1444,7 +1502,6 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
         }
     };
 
-    const int wave = tid >> 6, lane = tid & 63;
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, h = lane >> 5;
     f32x16 acc[NT][FM][FN];
@@ -1457,22 +1514,27 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[t][i][j][r] = 0.f;
 
-    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
     if (kt_begin < kt_end) {
-        compute_offsets(kt_begin, 0);
+        if (wave_u == 0) table_pass(kt_begin);
+        table_step();
         __syncthreads();
         load_global(0);
-        compute_offsets(kt_begin + 1, 1);
         store_lds(0);
         __syncthreads();
         for (int kt = kt_begin; kt < kt_end; ++kt) {
-            const int buf = (kt - kt_begin) & 1;
+            const int j = kt - kt_begin, buf = j & 1;
             const bool more = kt + 1 < kt_end;
-            // (the offset table of slice kt + 2 BEFORE the requests of slice kt + 1: at 168 registers its index arithmetic reloads a
-            //  spilled value from scratch, scratch loads retire through the same in-order counter as the global ones, and the
-            //  reload's wait would cover the four requests just issued -- the whole memory latency in front of this slice's MFMAs)
-            compute_offsets(kt + 2, buf);
-            if (more) load_global(buf ^ 1);
+            // every fourth slice the table of slices kt + 4 .. kt + 7, the four waves in turn: its ring slots were last read for the
+            // requests of slice kt - 1 (two barriers ago) and are first read for slice kt + 4 at slice kt + 3 (three barriers on).
+            // (the table BEFORE the requests of slice kt + 1: at 168 registers the three-tap form's index arithmetic reloads a spilled
+            //  value from scratch, scratch loads retire through the same in-order counter as the global ones, and the reload's wait
+            //  would cover the four requests just issued -- the whole memory latency in front of this slice's MFMAs)
+            if ((j & 3) == 0 && kt + 4 < kt_end) {
+                walker_scalar();
+                if (wave_u == (((j >> 2) + 1) & 3)) table_pass(kt + 4);
+                table_step();
+            }
+            if (more) load_global((j + 1) & (NSLOT - 1));
             const char* Ab = smem + buf * BUF;
             const char* Bb = Ab + 3 * A_PL;
             // fragments: dz rows (wm * FM + i) * 32 + li, chunk h; x row wn * 32 + li, entries 8h .. 8h + 9
@@ -2215,7 +2277,7 @@ extern "C" int erd_conv_wgrad(const erd_wgrad_desc* d, erd_stream_t stream) {
         const int nslices = erd_wgrad_row3_slices(d);
         const int fm = d->Cout > 64 ? 2 : 1;
         const int nci = (d->Cin + 63) / 64, nco = (d->Cout + fm * 64 - 1) / (fm * 64);
-        const size_t lds = (size_t)2 * 3 * (fm * 64 * 32 + 64 * 48) + 2 * (16 + 18) * sizeof(int);
+        const size_t lds = (size_t)2 * 3 * (fm * 64 * 32 + 64 * 48) + 8 * (16 + 20) * sizeof(int);      // (a ring of 8 table slots)
         void (*kern)(const erd_wgrad_desc, const int) = fm == 2 ? conv_wgrad_row3_x3_kernel<2, 1, true> : conv_wgrad_row3_x3_kernel<1, 1, true>;
         static bool attr_done3[2] = {false, false};
         if (!attr_done3[fm - 1]) {
@@ -2232,7 +2294,9 @@ extern "C" int erd_conv_wgrad(const erd_wgrad_desc* d, erd_stream_t stream) {
         // concatenated pixel axis
         const int nslices = (int)((npix + 15) / 16);
         const int nci = (d->Cin + 127) / 128, nco = (d->Cout + 127) / 128;
-        const size_t lds = (size_t)2 * 3 * (128 * 32 + 128 * 32) + 2 * (16 + 16) * sizeof(int);
+        for (int l = 0; l < d->nseg; ++l)      // (the kernel steps through the maps row by row)
+            ERD_REQUIRE(d->seg[l].N >= 1 && d->seg[l].GH >= 1 && d->seg[l].GW >= 1, "wgrad: empty map %d", l);
+        const size_t lds = (size_t)2 * 3 * (128 * 32 + 128 * 32) + 8 * (16 + 16) * sizeof(int);      // (a ring of 8 table slots)
         void (*kern)(const erd_wgrad_desc, const int) = conv_wgrad_row3_x3_kernel<2, 2, false>;
         static bool attr_done1 = false;
         if (!attr_done1) {
