@@ -41,14 +41,31 @@ __device__ __forceinline__ float pack_bf16(float a, float b) {
 constexpr int NTHREADS = 256;
 
 #ifdef ERD_IGEMM_TRACE      // debug builds only: per-workgroup phase cycles (tools/dbg/igemm_trace.py)
-__device__ unsigned long long g_igemm_trace[1024 * 8];
+constexpr int IG_NS = 32;   // slots per workgroup: 0-6 whole phases; 7-31 laps inside the three-limb K-slice (IG_LAP)
+__device__ unsigned long long g_igemm_trace[1024 * IG_NS];
 #define IG_T0(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#define IG_ACC(slot, v) if (threadIdx.x == 0 && blockIdx.x < 1024) g_igemm_trace[blockIdx.x * 8 + slot] += __builtin_amdgcn_s_memtime() - v
-#define IG_SET(slot, val) if (threadIdx.x == 0 && blockIdx.x < 1024) g_igemm_trace[blockIdx.x * 8 + slot] = (val)
+#define IG_ACC(slot, v) if (threadIdx.x == 0 && blockIdx.x < 1024) g_igemm_trace[blockIdx.x * IG_NS + slot] += __builtin_amdgcn_s_memtime() - v
+#define IG_SET(slot, val) if (threadIdx.x == 0 && blockIdx.x < 1024) g_igemm_trace[blockIdx.x * IG_NS + slot] = (val)
+// laps: wave-uniform accumulators (scalar registers, no branch in the loop body), written out once when the workgroup ends.  A lap is
+// pinned where it stands (sched_barrier) and reading the counter waits for every LDS read in flight: the stamps perturb what they
+// measure, so only differences between two builds that carry the same stamps mean anything.
+#define IG_LAPS_DECL unsigned ig_lap[IG_NS] = {}; unsigned ig_prev = 0
+#define IG_MARK() do { __builtin_amdgcn_sched_barrier(0); ig_prev = (unsigned)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define IG_LAP(slot) do { __builtin_amdgcn_sched_barrier(0); const unsigned t_ = (unsigned)__builtin_amdgcn_s_memtime();     \
+                          ig_lap[slot] += t_ - ig_prev; ig_prev = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
+#define IG_G_FIRST int ig_g = 0
+#define IG_G_NEXT ++ig_g
+#define IG_LAPS_STORE() for (int q_ = 7; q_ < IG_NS; ++q_) { IG_SET(q_, (unsigned long long)ig_lap[q_]); }
 #else
 #define IG_T0(v)
 #define IG_ACC(slot, v)
 #define IG_SET(slot, val)
+#define IG_LAPS_DECL
+#define IG_MARK()
+#define IG_LAP(slot)
+#define IG_G_FIRST
+#define IG_G_NEXT
+#define IG_LAPS_STORE()
 #endif
 
 struct RowInfo {
@@ -82,8 +99,11 @@ __device__ __forceinline__ float4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned 
 // middle of the K-slice that is supposed to hide the transfer.  An asm load is absent from the compiler's s_waitcnt bookkeeping, which
 // is safe in one direction only: loads retire in order, so the compiler's counted waits for ITS loads can only become stricter; the
 // DMA's own completion is waited for explicitly (`glds_wait_all`) in front of the barrier that publishes the buffer.  M0 is written
-// in the same statement (the compiler keeps nothing in M0 across statements); `s_nop 0`: the M0-write -> LDS-DMA hazard.
+// in the same statement and named as clobbered (nothing of the compiler's lives in M0 across it); `s_nop 0`: the M0-write -> LDS-DMA
+// hazard.  FRESH: the descriptor's scalar registers may have been written by a v_readfirstlane just before (the first request of a tile):
+// the five wait states of VALU-writes-SGPR -> VMEM-reads-it are the statement's own, the compiler pads nothing inside or in front of asm.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+template <bool B> struct bool_c { static constexpr bool value = B; };
 __device__ __forceinline__ i32x4 rsrc_words(const void* ptr, int bytes) {
     const unsigned long long a = (unsigned long long)ptr;
     i32x4 r;
@@ -93,8 +113,30 @@ __device__ __forceinline__ i32x4 rsrc_words(const void* ptr, int bytes) {
     r.w = 0x00020000;
     return r;
 }
+// (clang notes that M0 is a register it reserves; naming it is the point)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+template <bool FRESH = false>
 __device__ __forceinline__ void glds16(const i32x4 rs, unsigned lds_byte, unsigned voff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lds_byte), "v"(voff), "s"(rs) : "memory");
+    if constexpr (FRESH)
+        asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lds_byte), "v"(voff), "s"(rs)
+                     : "memory", "m0");
+    else
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lds_byte), "v"(voff), "s"(rs) : "memory", "m0");
+}
+// The same request, held in its place in an MFMA stream by two accumulators it pretends to touch: after the MFMA that wrote `after`, in
+// front of the next one that reads `before` (the compiler orders register-only instructions around asm through operands only).
+typedef float f32x16_t __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ void glds16(const i32x4 rs, unsigned lds_byte, unsigned voff, f32x16_t& after, f32x16_t& before) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, 0 offen lds"
+                 : "+v"(after), "+v"(before)
+                 : "s"(lds_byte), "v"(voff), "s"(rs)
+                 : "memory", "m0");
+}
+#pragma clang diagnostic pop
+template <bool FRESH, typename... T>
+__device__ __forceinline__ void glds16_sel(bool_c<FRESH>, const i32x4 rs, unsigned lds_byte, unsigned voff, T&... tie) {
+    if constexpr (sizeof...(T) == 0) glds16<FRESH>(rs, lds_byte, voff); else glds16(rs, lds_byte, voff, tie...);
 }
 __device__ __forceinline__ void glds_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
@@ -205,6 +247,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
     IG_T0(t_kernel);
     IG_SET(0, t_kernel);
     for (int q_ = 1; q_ < 8; ++q_) { IG_SET(q_, 0ull); }
+    IG_LAPS_DECL;
     for (long long u = u_begin; u < u_end;) {
         IG_T0(t_pro);
         const int tt = (int)(u / nkt);
@@ -270,35 +313,39 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
         // per-row byte offset of tap (0,0) and a validity bit per tap: the K loop then needs one add + one select
         // per 16-B load, and zero padding comes from the buffer's out-of-range rule (no branches, no zero fill)
         unsigned a_base[AJ], a_mask[AJ];
-#pragma unroll
-        for (int j = 0; j < AJ; ++j) {
-            RowInfo ri;
-            if constexpr (GL) {      // no table, no barriers: a thread decodes its own AJ rows (the operand region is about to be filled by DMA)
-                const int GHW = sg.GH * sg.GW;
-                const int m = mt * BM + r0 + RPP * j;
-                if (m < sg.N * GHW) {
-                    const int n = m / GHW;
-                    const int rem = m - n * GHW;
-                    const int a = rem / sg.GW;
-                    ri.in_off = (int)(n * sg.in_nstride);
-                    ri.ih0 = a * p.in_stride;
-                    ri.iw0 = (rem - a * sg.GW) * p.in_stride;
-                } else {
-                    ri.in_off = 0;
-                    ri.ih0 = -(1 << 28);
-                    ri.iw0 = -(1 << 28);
-                }
-            } else {
-                ri = rows[r0 + RPP * j];
-            }
-            a_base[j] = (unsigned)(ri.in_off + (ri.ih0 * IW + ri.iw0) * Cin + chunk_l * KPC) * ABYTES;
-            unsigned m = 0;
-            for (int t = 0; t < nt_s; ++t) {
-                const int ih = ri.ih0 + p.dy[tap_lo + t], iw = ri.iw0 + p.dx[tap_lo + t];
-                m |= ((unsigned)ih < (unsigned)IH && (unsigned)iw < (unsigned)IW) ? (1u << t) : 0u;
-            }
-            a_mask[j] = m;
+        // (spelled once, expanded at one of two places: a lambda here changes the code of the instantiations that do not move it)
+#define ERD_DECODE_ROWS                                                                                                                            \
+        _Pragma("unroll")                                                                                                                          \
+        for (int j = 0; j < AJ; ++j) {                                                                                                             \
+            RowInfo ri;                                                                                                                            \
+            if constexpr (GL) {      /* no table, no barriers: a thread decodes its own AJ rows (the operand region is filled by DMA) */   \
+                const int GHW = sg.GH * sg.GW;                                                                                                     \
+                const int m = mt * BM + r0 + RPP * j;                                                                                              \
+                if (m < sg.N * GHW) {                                                                                                              \
+                    const int n = m / GHW;                                                                                                         \
+                    const int rem = m - n * GHW;                                                                                                   \
+                    const int a = rem / sg.GW;                                                                                                     \
+                    ri.in_off = (int)(n * sg.in_nstride);                                                                                          \
+                    ri.ih0 = a * p.in_stride;                                                                                                      \
+                    ri.iw0 = (rem - a * sg.GW) * p.in_stride;                                                                                      \
+                } else {                                                                                                                           \
+                    ri.in_off = 0;                                                                                                                 \
+                    ri.ih0 = -(1 << 28);                                                                                                           \
+                    ri.iw0 = -(1 << 28);                                                                                                           \
+                }                                                                                                                                  \
+            } else {                                                                                                                               \
+                ri = rows[r0 + RPP * j];                                                                                                           \
+            }                                                                                                                                      \
+            a_base[j] = (unsigned)(ri.in_off + (ri.ih0 * IW + ri.iw0) * Cin + chunk_l * KPC) * ABYTES;                                             \
+            unsigned m = 0;                                                                                                                        \
+            for (int t = 0; t < nt_s; ++t) {                                                                                                       \
+                const int ih = ri.ih0 + p.dy[tap_lo + t], iw = ri.iw0 + p.dx[tap_lo + t];                                                          \
+                m |= ((unsigned)ih < (unsigned)IH && (unsigned)iw < (unsigned)IW) ? (1u << t) : 0u;                                                \
+            }                                                                                                                                      \
+            a_mask[j] = m;                                                                                                                         \
         }
+        // GL: the tile's first weight requests depend on nothing in the decode (two integer divisions per row): they go out in front of it
+        if constexpr (!GL) { ERD_DECODE_ROWS }
         const int n0 = nt * BN;
         unsigned b_base[X3 ? 1 : BJ];
         unsigned bx_base[X3 ? BJX : 1];            // f32x3: byte offset of (cout row, 8-value chunk) inside ONE bf16 weight plane
@@ -358,14 +405,14 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
         const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem;      // LDS byte address of the operand region
         const i32x4 rw_in = GL ? rsrc_words(in, (int)((long long)sg.N * sg.in_nstride * ABYTES)) : i32x4{0, 0, 0, 0};
         const i32x4 rw_w = GL ? rsrc_words(p.w_x3, (int)((long long)p.Cout * p.wrow * 6)) : i32x4{0, 0, 0, 0};
-        auto glds_a = [&](int j, const int buf) {
+        auto glds_a = [&](int j, const int buf, auto&... tie) {
             const bool ok = cok && ((a_mask[j] >> ctap) & 1u);
-            glds16(rw_in, lds0 + (unsigned)(((buf * BM + RPP * j + 8 * wave_s) * CH) * 16), ok ? a_base[j] + (unsigned)adelta : OOB);
+            glds16(rw_in, lds0 + (unsigned)(((buf * BM + RPP * j + 8 * wave_s) * CH) * 16), ok ? a_base[j] + (unsigned)adelta : OOB, tie...);
         };
-        auto glds_b = [&](int j, const int buf) {      // j = plane * BJX + row pass
+        auto glds_b = [&](int j, const int buf, auto fresh, auto&... tie) {      // j = plane * BJX + row pass
             const int pl = j / BJX, jj = j - pl * BJX;
-            glds16(rw_w, lds0 + (unsigned)((2 * BM * CH + (buf * 3 + pl) * BN * CHB + (RPPB * jj + 16 * wave_s) * CHB) * 16),
-                   cokb ? bx_base[X3 ? jj : 0] + (unsigned)bdelta + (unsigned)pl * plane_b : OOB);
+            glds16_sel(fresh, rw_w, lds0 + (unsigned)((2 * BM * CH + (buf * 3 + pl) * BN * CHB + (RPPB * jj + 16 * wave_s) * CHB) * 16),
+                   cokb ? bx_base[X3 ? jj : 0] + (unsigned)bdelta + (unsigned)pl * plane_b : OOB, tie...);
         };
         auto load_a = [&](int j, const int set) {
             const bool ok = cok && ((a_mask[j] >> ctap) & 1u);
@@ -416,12 +463,22 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-        slice_begin();
+#ifdef ERD_GLP_BURST           // (timing probe: see k_slice_x3)
+        constexpr bool SPLIT = false;
+#else
+        constexpr bool SPLIT = GL;
+#endif
+        if constexpr (!GL) slice_begin();
         if constexpr (GL) {
+            slice_begin();
+            glds_b(0, 0, bool_c<true>{});
 #pragma unroll
-            for (int j = 0; j < NBL; ++j) glds_b(j, 0);
+            for (int j = 1; j < NBL; ++j) glds_b(j, 0, bool_c<false>{});
+            { ERD_DECODE_ROWS }      // (under the weight requests' latency)
 #pragma unroll
             for (int j = 0; j < AJ; ++j) glds_a(j, 0);
+            glds_wait_all();
+#undef ERD_DECODE_ROWS
         } else {
 #pragma unroll
         for (int j = 0; j < AJ; ++j) load_a(j, 0);
@@ -435,7 +492,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
 #pragma unroll
             for (int j = 0; j < NBL; ++j) load_b(j, NSET - 1);
         }
-        if constexpr (GL) glds_wait_all(); else store_lds(0, 0);
+        if constexpr (!GL) store_lds(0, 0);
         __syncthreads();
 
         IG_ACC(2, t_pro);
@@ -445,10 +502,41 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
         // f32x3: one K-slice = two k16 steps.  A lane owns pixel row li of its wave's 32 rows and the 8 channels 16 s + 8 h ..
         // + 7 of step s: two 16-B reads of fp32 values, split into three bf16x8 limbs (round-to-nearest: cvt_pk / sub, exact), and
         // three 16-B reads per cout block of the pre-split weights; then six MFMAs per block, smallest terms first.
-        auto k_slice_x3 = [&](const int kt, const int par) {
+        // GL, where the next slice's ten (128 x 64: seven) LDS-DMA requests go.  Each is s_mov m0 + s_nop + the load.  Round 6 issued them as
+        // two bursts of five behind the read batches at the head of each k16 step, under `if (more)`; the compiler then sinks the second
+        // step's MFMAs below the slice's wait + barrier, so the second burst was waited for (`vmcnt(0)`) right behind its issue
+        // (profiles/r08_igemm_dma_placement.txt).  Now they are issued ONE PER GAP of the FIRST k16 step's MFMA stream -- behind MFMA j of a
+        // limb group for the j that ERD_GLP_SLOTS names, never at a group's end, where the fragment reads of the next step sit -- in
+        // straight-line code: whether a next slice exists is a property of the CALL SITE (MORE: the last slice of a tile runs its own copy
+        // of the body, without requests), so no branch cuts the step into scheduling regions.  A request is held in its gap by two
+        // accumulators it names as operands (glds16: sched_barrier does not hold MFMAs on either side of an asm statement here).
+        // Every request has the second k16 step to land before the slice's `vmcnt(0)`.  Weights first: their addresses are ready at the
+        // top of the slice, the activation offsets need the tap's mask select.
+        // ERD_GLP_BURST (timing probe, tools/build_probe.sh): round 6's placement.
+#ifndef ERD_GLP_SLOTS
+#define ERD_GLP_SLOTS 0x5      // bit j: a request goes behind MFMA j of each limb group (four per group at 128 x 128, two at 128 x 64)
+#endif
+#ifndef ERD_GLP_AFIRST
+#define ERD_GLP_AFIRST 0       // (probe) 1: activation requests before weight requests
+#endif
+        constexpr int NP = AJ + NBL;      // requests per slice
+        // request slots of a k16 step: behind MFMA j of each of its six limb groups, for the j that the mask names (128 x 64: both MFMAs)
+        constexpr unsigned GLP_SLOTS = FN >= 4 ? (unsigned)(ERD_GLP_SLOTS) : 0x3u;
+        constexpr int GLP_NSLOT = 6 * __builtin_popcount(GLP_SLOTS & ((1u << FN) - 1u));
+        static_assert(!SPLIT || NP <= GLP_NSLOT, "a slice's requests do not fit the MFMA gaps of its first k16 step");
+        auto k_slice_x3 = [&](const int kt, const int par, auto more_c) {
+            constexpr bool MORE = decltype(more_c)::value;      // (meaningful with SPLIT only)
             const int buf = par;
-            const bool more = kt + 1 < ke;
+            const bool more = SPLIT ? MORE : kt + 1 < ke;
             if (more) slice_begin();
+            IG_MARK();
+            int np = 0;      // requests issued so far (a compile-time value once the step is unrolled)
+            auto request = [&](const int i, const int j) {      // behind MFMA j of a limb group, in front of MFMA j + 1
+                const int ia = ERD_GLP_AFIRST ? i : i - NBL, ib = ERD_GLP_AFIRST ? i - AJ : i;
+                f32x16 &t0 = acc[0][j], &t1 = acc[0][(j + 1) % FN];
+                if (ia >= 0 && ia < AJ) glds_a(ia, buf ^ 1, t0, t1);
+                if (ib >= 0 && ib < NBL) glds_b(ib, buf ^ 1, bool_c<false>{}, t0, t1);
+            };
             const float4* Ab = As + buf * BM * CH;
             const float4* Bb = Bs + buf * 3 * BN * CHB;
             const int arow = wm * 32 + li;
@@ -486,8 +574,11 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
             _Pragma("unroll") for (int j = 0; j < FN; ++j) acc[0][j][PL] += wb[j][PL].x * __builtin_bit_cast(float4, AV).x;
 #else
 #define ERD_X3(AV, PL)                                                                                              \
-            _Pragma("unroll") for (int j = 0; j < FN; ++j)                                                          \
-                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AV, __builtin_bit_cast(bf16x8, wb[j][PL]), acc[0][j], 0, 0, 0);
+            _Pragma("unroll") for (int j = 0; j < FN; ++j) {                                                        \
+                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AV, __builtin_bit_cast(bf16x8, wb[j][PL]), acc[0][j], 0, 0, 0); \
+                if constexpr (SPLIT && MORE) { if (((GLP_SLOTS >> j) & 1) && np < NP) request(np++, j); }   \
+            }                                                                                                       \
+            IG_LAP(16 + 6 * kk + ig_g); IG_G_NEXT;
 #endif
             float x[8], xn[8];
             read_a(0, x);
@@ -500,16 +591,21 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
                 // v_perm and the fragments are ready), the remainders r1 = x - hi, r2 = r1 - mid are computed under their
                 // MFMAs.  A weight plane's fragments are re-read for the next k16 step as soon as its last product is issued.
                 if (kk == 0) read_a(1, xn);
+                IG_LAP(8 + kk);       // the read batch
 #ifndef ERD_X3_NOLOAD     // (timing probe: the K loop re-uses the first slice's registers)
+                if constexpr (!SPLIT) {      // (SPLIT: ERD_X3 issues them)
                 if (more) {      // the next slice's global loads, half of them per k16 step, issued under this step's MFMAs
 #pragma unroll
                     for (int q = 0; q < APS; ++q)
                         if (kk * APS + q < AJ) { if constexpr (GL) glds_a(kk * APS + q, buf ^ 1); else load_a(kk * APS + q, 0); }
 #pragma unroll
                     for (int q = 0; q < BPS; ++q)
-                        if (kk * BPS + q < NBL) { if constexpr (GL) glds_b(kk * BPS + q, buf ^ 1); else load_b(kk * BPS + q, 0); }
+                        if (kk * BPS + q < NBL) { if constexpr (GL) glds_b(kk * BPS + q, buf ^ 1, bool_c<false>{}); else load_b(kk * BPS + q, 0); }
+                }
                 }
 #endif
+                IG_LAP(10 + kk);      // the request burst (ERD_GLP_BURST; nothing otherwise)
+                IG_G_FIRST;
                 u4v ph, pm, pl;
                 const bf16x8 ah = limb(x, ph);
                 ERD_X3(ah, 2)
@@ -551,8 +647,11 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
             }
 #undef ERD_X3
 #ifndef ERD_X3_NOSYNC     // (timing probe, with ERD_X3_NOLOAD: no LDS refill and no barrier between slices)
+            IG_LAP(12);           // what is left of the step behind its last stamp
             if constexpr (GL) glds_wait_all(); else { if (more) store_lds(buf ^ 1, 0); }
+            IG_LAP(13);           // GL: the wait for the requests
             __syncthreads();      // (GL: everybody's DMA into the other buffer has landed, and this buffer is free)
+            IG_LAP(7);            // the barrier
 #endif
         };
         // one K-slice; par = (kt - ks) & 1 selects the LDS buffer (and, with two slices in flight, the register set)
@@ -629,8 +728,11 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
             __syncthreads();
 #endif
         };
-        if constexpr (X3) {
-            for (int kt = ks; kt < ke; ++kt) k_slice_x3(kt, (kt - ks) & 1);
+        if constexpr (X3 && SPLIT) {      // MORE: a next slice exists
+            for (int kt = ks; kt + 1 < ke; ++kt) k_slice_x3(kt, (kt - ks) & 1, bool_c<true>{});
+            k_slice_x3(ke - 1, (ke - 1 - ks) & 1, bool_c<false>{});
+        } else if constexpr (X3) {
+            for (int kt = ks; kt < ke; ++kt) k_slice_x3(kt, (kt - ks) & 1, bool_c<false>{});
         } else if constexpr (PD2) {
             for (int kt = ks; kt < ke; kt += 2) {       // unrolled by two: register sets are named at compile time
                 k_slice(kt, 0);
@@ -641,7 +743,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
         }
 
         IG_ACC(3, t_loop);
-        IG_SET(6, g_igemm_trace[blockIdx.x * 8 + 6] + (unsigned long long)(ke - ks));
+        IG_SET(6, g_igemm_trace[blockIdx.x * IG_NS + 6] + (unsigned long long)(ke - ks));
         IG_T0(t_fix);
         // ---- partial tile: hand the accumulators over; the last contributor to arrive reduces ----------
         if (ks != 0 || ke != nkt_t) {
@@ -936,6 +1038,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
         IG_ACC(5, t_epi);
         IG_SET(1, __builtin_amdgcn_s_memtime());
     }
+    IG_LAPS_STORE();
 }
 
 // -------------------------------------------------------------------------------------------------
