@@ -64,6 +64,10 @@ class WeightPrepItem(C.Structure):
                 ("Cout", i32), ("ntaps", i32), ("Cin", i32), ("flip", i32), ("kind", i32), ("block0", i32)]
 
 
+class ResizeItem(C.Structure):
+    _fields_ = [("offset", i64), ("sh", i32), ("sw", i32), ("nh", i32), ("nw", i32), ("flip", i32), ("reserved", i32)]
+
+
 class Levels(C.Structure):
     _fields_ = [("nseg", i32), ("off", i64 * ERD_MAX_SEG), ("cnt", i64 * ERD_MAX_SEG)]
 
@@ -135,6 +139,7 @@ _SIGNATURES = {
     "erd_loss_finalize": [P, P, P, P, P, i32, i32, i32, f32, f32, f32, f32, f32, P, P, P, P],
     "erd_preprocess_image": [P, i32, i32, i32, P, i32, i32, P, P, i32, f32, P],
     "erd_resize_normalize": [P, i32, i32, P, P, P, P, i32, i32, P, i32, i32, P, P, i32, i32, f32, P],
+    "erd_resize_normalize_batch": [P, i64, P, i32, P, i32, i32, P, P, i32, f32, P],
     "erd_predict_ws_bytes": [i32, i32, i32],
     "erd_predict_topk": [P, P, P, i32, i64, i32, P, P, P, f32, i32, P, P, P, P, P, C.c_size_t, P],
     "erd_predict_nms": [P, P, P, P, i32, i32, P, f32, f32, i32, P, P, P, P, C.c_size_t, P],

@@ -1004,6 +1004,111 @@ extern "C" int erd_resize_normalize(const void* src_hwc_u8, int sh, int sw, cons
     return erd::check_launch("resize_normalize");
 }
 
+namespace {
+// One axis of datasets.linear_coeffs for ONE output index d, bit for bit: scale = 1.0 / (double(dst) / double(src)) as the caller
+// formed it, f = float((d + 0.5) * scale - 0.5) with the product and the difference rounded SEPARATELY in double (numpy evaluates
+// them as two array operations; a contracted v_fma_f64 is a different function), floor, the two clamps, then the 11-bit weights
+// c1 = rint(double(f) * 2048), c0 = rint(double(float(1.0f - f)) * 2048) (round half to even, as np.rint).
+// The product and the difference are written as OPERATORS under `fp contract(off)`: __dmul_rn / __dsub_rn are inline `x * y` / `x - y`
+// in this toolchain's headers, compiled there with contraction allowed, and came out of this function fused (v_fma_f64 in the ISA).
+__device__ __forceinline__ void linear_coeff(int d, double scale, int src, int& ofs, int& c0, int& c1) {
+#pragma clang fp contract(off)
+    const double t = ((double)d + 0.5) * scale;
+    float f = (float)(t - 0.5);
+    int s = (int)floorf(f);
+    f = __fsub_rn(f, (float)s);
+    if (s < 0) { f = 0.f; s = 0; }
+    if (s >= src - 1) { f = 0.f; s = src - 1; }
+    ofs = s;
+    c1 = (int)rint((double)f * 2048.0);
+    c0 = (int)rint((double)__fsub_rn(1.0f, f) * 2048.0);
+}
+
+__device__ __forceinline__ double linear_scale(int src, int dst) {
+    return __ddiv_rn(1.0, __ddiv_rn((double)dst, (double)src));
+}
+
+// resize_normalize_kernel over a whole batch in one launch, without host-built tables: blockIdx.y is the image, a thread owns four
+// consecutive x of one row of the padded [3][H][W] slot and computes its own coefficients (one y set, four x sets).  The pixel
+// arithmetic is resize_normalize_kernel's.  VEC: W % 4 == 0 and a 16-byte aligned output, so each plane gets one float4 store;
+// otherwise scalar stores with the row end checked.  A record that does not fit the source buffer reads nothing (its slot is padding).
+template <bool VEC>
+__global__ __launch_bounds__(256) void resize_normalize_batch_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                                     const erd_resize_item* __restrict__ items,
+                                                                     float* __restrict__ out, int H, int W, float m0, float m1,
+                                                                     float m2, float s0, float s1, float s2, int swap_rb,
+                                                                     float pad_value) {
+    const int W4 = (W + 3) >> 2;
+    const int64_t i = blockIdx.x * 256ll + threadIdx.x;
+    if (i >= (int64_t)H * W4) return;
+    const int y = (int)(i / W4), x = (int)(i - (int64_t)y * W4) * 4;
+    const erd_resize_item it = items[blockIdx.y];
+    const int sh = it.sh, sw = it.sw, nh = it.nh, nw = it.nw;
+    const bool ok = sh > 0 && sw > 0 && nh > 0 && nw > 0 && it.offset >= 0 && it.offset + (int64_t)sh * sw * 3 <= src_bytes;
+    const int64_t plane = (int64_t)H * W;
+    float* o = out + (int64_t)blockIdx.y * 3 * plane + (int64_t)y * W + x;
+    float v[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[c][j] = pad_value;
+    if (ok && y < nh && x < nw) {
+        int y0, b0, b1;
+        linear_coeff(y, linear_scale(sh, nh), sh, y0, b0, b1);
+        const int y1 = min(y0 + 1, sh - 1);
+        const uint8_t* r0 = src + it.offset + (int64_t)y0 * sw * 3;
+        const uint8_t* r1 = src + it.offset + (int64_t)y1 * sw * 3;
+        const double xscale = linear_scale(sw, nw);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (x + j >= nw) continue;
+            const int xs = it.flip ? nw - 1 - (x + j) : x + j;          // flipping the resized image == reading it mirrored
+            int x0, a0, a1;
+            linear_coeff(xs, xscale, sw, x0, a0, a1);
+            const int x1 = min(x0 + 1, sw - 1);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int cs = swap_rb ? 2 - c : c;
+                const int t0 = r0[x0 * 3 + cs] * a0 + r0[x1 * 3 + cs] * a1;
+                const int t1 = r1[x0 * 3 + cs] * a0 + r1[x1 * 3 + cs] * a1;
+                int u = (((b0 * (t0 >> 4)) >> 16) + ((b1 * (t1 >> 4)) >> 16) + 2) >> 2;
+                u = min(max(u, 0), 255);
+                const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
+                v[c][j] = __fdiv_rn(__fsub_rn((float)u, mean), sd);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (VEC) {
+            *reinterpret_cast<float4*>(o + c * plane) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x + j < W) o[c * plane + j] = v[c][j];
+        }
+    }
+}
+}  // namespace
+
+extern "C" int erd_resize_normalize_batch(const void* src_u8, int64_t src_bytes, const erd_resize_item* items_dev, int n,
+                                          float* out, int H, int W, const float* mean3, const float* std3, int swap_rb,
+                                          float pad_value, erd_stream_t stream) {
+    ERD_REQUIRE(src_u8 && items_dev && out && mean3 && std3, "resize_normalize_batch: null");
+    ERD_REQUIRE(src_bytes > 0 && n > 0 && n <= 65535 && H > 0 && W > 0, "resize_normalize_batch: bad sizes");
+    const int64_t work = (int64_t)H * ((W + 3) / 4);
+    const dim3 grid((unsigned)((work + 255) / 256), (unsigned)n);
+    const bool vec = W % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    const uint8_t* s = reinterpret_cast<const uint8_t*>(src_u8);
+    if (vec)
+        hipLaunchKernelGGL(resize_normalize_batch_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, s, src_bytes, items_dev,
+                           out, H, W, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], swap_rb, pad_value);
+    else
+        hipLaunchKernelGGL(resize_normalize_batch_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, s, src_bytes, items_dev,
+                           out, H, W, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], swap_rb, pad_value);
+    return erd::check_launch("resize_normalize_batch");
+}
+
 extern "C" int erd_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps,
                            float* scale, float* shift, int64_t n, erd_stream_t stream) {
     ERD_REQUIRE(gamma && beta && mean && var && scale && shift, "bn_fold: null");

@@ -152,8 +152,8 @@ class AspectRatioBatchSampler:
 # ---------------------------------------------------------------------------------------------------------
 # image side: LoadImageFromFile -> Resize(scale=(1333, 800), keep_ratio=True) -> RandomFlip(0.5) -> PackDetInputs ->
 # DetDataPreprocessor (configs/gfl_increment/*:13-19, data_preprocessor.py:110-183).  Decode stays on the host (PIL; the
-# reference decodes with cv2 on the host too); resize + flip + normalise + pad are one kernel over the padded batch slot
-# (erd_resize_normalize).  cv2's 8-bit bilinear resize is restated (resize.cpp: half-pixel centres, 11-bit fixed-point
+# reference decodes with cv2 on the host too); resize + flip + normalise + pad are one kernel over the padded batch
+# (erd_resize_normalize_batch: one launch per training batch; erd_resize_normalize per image for test-time views).  cv2's 8-bit bilinear resize is restated (resize.cpp: half-pixel centres, 11-bit fixed-point
 # weights, two-pass rounding) -- UNPINNED against cv2, which is not in this image.
 # ---------------------------------------------------------------------------------------------------------
 def linear_coeffs(src: int, dst: int):
@@ -215,14 +215,107 @@ def pinned(im: np.ndarray):
     return t.pin_memory() if torch.cuda.is_available() else t
 
 
+# one record of erd_resize_normalize_batch (include/erd_hip.h erd_resize_item, _lib.ResizeItem): 32 bytes
+RESIZE_ITEM = np.dtype([("offset", "<i8"), ("sh", "<i4"), ("sw", "<i4"), ("nh", "<i4"), ("nw", "<i4"), ("flip", "<i4"),
+                        ("reserved", "<i4")])
+
+
+class PackedBatch:
+    """host half of a batch as ONE buffer: the records {offset, sh, sw, nh, nw, flip} at its head, then the decoded uint8 HWC
+    images back to back at 16-byte aligned offsets.  `buf` is page-locked when a GPU is present, so the single host-to-device
+    copy of `assemble` is asynchronous.  `metas[k]` = (sh, sw, nh, nw, flip) of image k, as Python ints / bool."""
+
+    def __init__(self, buf: torch.Tensor, metas: list):
+        self.buf, self.metas = buf, metas
+
+    def __len__(self):
+        return len(self.metas)
+
+
+def pack_images(imgs: Sequence, metas: Sequence[tuple]) -> PackedBatch:
+    """imgs: decoded [h,w,3] uint8 arrays (or CPU tensors); metas: (nh, nw, flip) per image"""
+    n = len(imgs)
+    arrs = [(im.numpy() if isinstance(im, torch.Tensor) else np.asarray(im)) for im in imgs]
+    offs, pos = [], -(-n * RESIZE_ITEM.itemsize // 16) * 16
+    for a in arrs:
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"decoded images are uint8 [h, w, 3], got {a.dtype} {a.shape}")
+        offs.append(pos)
+        pos += -(-a.size // 16) * 16
+    buf = torch.empty(pos, dtype=torch.uint8, pin_memory=torch.cuda.is_available())      # torch's pinned allocator, as pinned()
+    host = buf.numpy()
+    rec = host[:n * RESIZE_ITEM.itemsize].view(RESIZE_ITEM)
+    full = []
+    for k, (a, o, (nh, nw, flip)) in enumerate(zip(arrs, offs, metas)):
+        host[o:o + a.size] = a.reshape(-1)
+        rec[k] = (o, a.shape[0], a.shape[1], nh, nw, int(bool(flip)), 0)
+        full.append((int(a.shape[0]), int(a.shape[1]), int(nh), int(nw), bool(flip)))
+    return PackedBatch(buf, full)
+
+
+class ScaleSampler:
+    """the target scale of one image, drawn from that image's own generator AFTER its flip draw.  The rules restate mmcv 2.x
+    transforms/processing.py (RandomResize._random_sample / _random_sample_ratio, RandomChoiceResize._random_select) --
+    UNPINNED: mmcv is not part of this project's test oracle.
+      Resize(scale):                              the scale, no draw
+      RandomResize(scale=[(a, b), (c, d)]):       (randint(min(a, c), max(a, c) + 1), randint(min(b, d), max(b, d) + 1)), in that order
+      RandomResize(scale=(a, b), ratio_range):    r = random_sample() * (hi - lo) + lo; (int(a * r), int(b * r))
+      RandomChoiceResize(scales):                 scales[randint(len(scales))]"""
+
+    def __init__(self, type: str = "Resize", scale=None, ratio_range=None, scales=None):
+        self.type = type
+        if type == "Resize":
+            self.scale = _scale2(scale)
+        elif type == "RandomResize" and ratio_range is not None:
+            self.scale, self.ratio_range = _scale2(scale), (float(ratio_range[0]), float(ratio_range[1]))
+            if not 0 < self.ratio_range[0] <= self.ratio_range[1]:
+                raise ValueError(f"RandomResize: ratio_range {ratio_range} is not 0 < lo <= hi")
+        elif type == "RandomResize":
+            if not isinstance(scale, (list, tuple)) or len(scale) != 2:
+                raise ValueError(f"RandomResize: scale is two (w, h) tuples or one with ratio_range, got {scale}")
+            self.scale, self.ratio_range = (_scale2(scale[0]), _scale2(scale[1])), None
+        elif type == "RandomChoiceResize":
+            if not isinstance(scales, (list, tuple)) or not scales:
+                raise ValueError(f"RandomChoiceResize: scales is a non-empty list of (w, h), got {scales}")
+            self.scales = [_scale2(s) for s in scales]
+        else:
+            raise ValueError(f"resize stage {type!r} is not built")
+
+    def __call__(self, rng: np.random.RandomState) -> tuple:
+        if self.type == "Resize":
+            return self.scale
+        if self.type == "RandomChoiceResize":
+            return self.scales[rng.randint(len(self.scales))]
+        if self.ratio_range is not None:
+            lo, hi = self.ratio_range
+            r = rng.random_sample() * (hi - lo) + lo
+            return int(self.scale[0] * r), int(self.scale[1] * r)
+        (a, b), (c, d) = self.scale
+        e0 = rng.randint(min(a, c), max(a, c) + 1)
+        e1 = rng.randint(min(b, d), max(b, d) + 1)
+        return int(e0), int(e1)
+
+    def __repr__(self):
+        return "ScaleSampler(%s)" % ", ".join(f"{k}={v!r}" for k, v in vars(self).items())
+
+
+def _scale2(s) -> tuple:
+    if not isinstance(s, (list, tuple)) or len(s) != 2 or not all(isinstance(v, (int, np.integer)) and v > 0 for v in s):
+        raise ValueError(f"a scale is (w, h) in positive integers, got {s!r}")
+    return int(s[0]), int(s[1])
+
+
 class GpuDetPipeline:
     """one training batch from image indices: decoded images -> normalised, padded [N,3,H,W] fp32 on the GPU + data
-    samples with resized / flipped / clipped boxes.  Deterministic given `seed` (flip decisions per (epoch, index))."""
+    samples with resized / flipped / clipped boxes.  Deterministic given `seed`: image `index` of `epoch` has its own
+    generator, whose first draw is the flip and whose later draws (if any) are the scale -- whichever batch it falls into."""
 
     def __init__(self, annotations: CocoAnnotations, scale=(1333, 800), flip_prob: float = 0.5, mean=(123.675, 116.28, 103.53),
                  std=(58.395, 57.12, 57.375), bgr_to_rgb: bool = True, pad_size_divisor: int = 32, pad_value: float = 0.0,
-                 seed: int = 0, loader=load_image_bgr, device="cuda"):
+                 seed: int = 0, loader=load_image_bgr, device="cuda", scale_sampler: Optional[ScaleSampler] = None):
+        """scale_sampler: a per-image scale (RandomResize / RandomChoiceResize); None = the fixed `scale`"""
         self.ann, self.scale, self.flip_prob = annotations, tuple(scale), flip_prob
+        self.scale_sampler = scale_sampler
         self.mean = [float(np.float32(v)) for v in mean]
         self.std = [float(np.float32(v)) for v in std]
         self.swap, self.div, self.pad_value, self.seed = bgr_to_rgb, pad_size_divisor, pad_value, seed
@@ -245,25 +338,44 @@ class GpuDetPipeline:
         """host half of a batch (LoadImageFromFile): safe to run on worker threads, PIL releases the GIL while decoding"""
         return [self.loader(self.ann.get_data_info(i)["img_path"]) for i in indices]
 
+    def draw(self, index: int, epoch: Optional[int] = None) -> tuple:
+        """(flip, scale) of image `index` in `epoch`: the flip is the generator's FIRST draw (so fixed-scale runs flip as they
+        always did), the scale draws follow it"""
+        epoch = self.epoch if epoch is None else epoch
+        rng = np.random.RandomState((self.seed * 1000003 + epoch * 7919 + int(index)) % (2 ** 31 - 1))
+        flip = bool(rng.rand() < self.flip_prob)
+        return flip, (self.scale if self.scale_sampler is None else tuple(self.scale_sampler(rng)))
+
+    def pack(self, indices: Sequence[int], imgs: Optional[Sequence[np.ndarray]] = None, epoch: Optional[int] = None) -> PackedBatch:
+        """host half of a batch, ready for ONE copy and ONE launch: decode (unless `imgs` is given), draw flip and scale per
+        image, pack pixels and records into one page-locked buffer.  Safe on worker threads."""
+        imgs = self.decode(indices) if imgs is None else imgs
+        metas = []
+        for i, im in zip(indices, imgs):
+            flip, scale = self.draw(i, epoch)
+            nw, nh = rescale_size((im.shape[1], im.shape[0]), scale)
+            metas.append((nh, nw, flip))
+        return pack_images(imgs, metas)
+
     def batch(self, indices: Sequence[int]):
         return self.assemble(indices, self.decode(indices))
 
-    def assemble(self, indices: Sequence[int], imgs: Sequence[np.ndarray]):
-        """device half: resize / flip / normalise / pad kernels + the data samples"""
+    def assemble(self, indices: Sequence[int], imgs):
+        """device half: one host-to-device copy, one resize / flip / normalise / pad launch over the whole batch
+        (erd_resize_normalize_batch: bit-identical to one erd_resize_normalize launch per image) + the data samples.
+        imgs: what `pack` returned, or the decoded images themselves (packed here)."""
         from . import kernels as K
-        new = [rescale_size((im.shape[1], im.shape[0]), self.scale) for im in imgs]          # (w, h)
-        H = max(int(math.ceil(h / self.div)) * self.div for _, h in new)
-        W = max(int(math.ceil(w / self.div)) * self.div for w, _ in new)
-        out = torch.empty((len(imgs), 3, H, W), dtype=torch.float32, device=self.device)
+        packed = imgs if isinstance(imgs, PackedBatch) else self.pack(indices, imgs)
+        if len(packed) != len(indices):
+            raise ValueError(f"{len(indices)} indices for a packed batch of {len(packed)}")
+        H = max(int(math.ceil(nh / self.div)) * self.div for _, _, nh, _, _ in packed.metas)
+        W = max(int(math.ceil(nw / self.div)) * self.div for _, _, _, nw, _ in packed.metas)
+        out = torch.empty((len(packed), 3, H, W), dtype=torch.float32, device=self.device)
+        K.resize_normalize_batch(packed.buf.to(self.device, non_blocking=True), len(packed), out, self.mean, self.std, self.swap,
+                                 self.pad_value)
         samples = []
-        for k, (i, im, (nw, nh)) in enumerate(zip(indices, imgs, new)):
-            rng = np.random.RandomState((self.seed * 1000003 + self.epoch * 7919 + int(i)) % (2 ** 31 - 1))
-            flip = bool(rng.rand() < self.flip_prob)
-            src = (im if isinstance(im, torch.Tensor) else torch.from_numpy(im)).to(self.device, non_blocking=True)
-            K.resize_normalize_into(src, self._table(im.shape[0], im.shape[1], nh, nw), (nh, nw), out[k], self.mean, self.std,
-                                    flip, self.swap, self.pad_value)
-            s = self.ann.data_sample(i, scale_factor=(nw / im.shape[1], nh / im.shape[0]), flip=flip, img_shape=(nh, nw),
-                                     clip=True)
+        for i, (sh, sw, nh, nw, flip) in zip(indices, packed.metas):
+            s = self.ann.data_sample(i, scale_factor=(nw / sw, nh / sh), flip=flip, img_shape=(nh, nw), clip=True)
             s.set_metainfo(dict(pad_shape=(H, W), batch_input_shape=(H, W)))
             samples.append(s)
         return out, samples
@@ -366,3 +478,71 @@ def resolve_tta(cfg) -> dict:
     if not tta:
         raise ValueError("--tta: tta_pipeline has no TestTimeAug")
     return dict(tta_model=tta_model, scales=scales or [outer or base], flips=flips or [False])
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the train pipeline of a config, read (not run) -- the training twin of resolve_tta
+# ---------------------------------------------------------------------------------------------------------
+_RESIZE_KINDS = ("Resize", "RandomResize", "RandomChoiceResize")
+_RESIZE_KEYS = {"Resize": {"scale"}, "RandomResize": {"scale", "ratio_range"}, "RandomChoiceResize": {"scales"}}
+
+
+def _plain(t) -> dict:
+    return t.to_dict() if hasattr(t, "to_dict") else dict(t)
+
+
+def _train_resize(t: dict) -> ScaleSampler:
+    kind = t["type"]
+    if t.get("keep_ratio", False) is not True:
+        raise ValueError(f"train pipeline: {kind} is built with keep_ratio=True only, got {t}")
+    if t.get("clip_object_border", True) is not True or t.get("interpolation", "bilinear") != "bilinear" \
+            or t.get("backend", "cv2") != "cv2" or t.get("resize_type", "Resize") != "Resize":
+        raise ValueError(f"train pipeline: {kind} is built with bilinear cv2 interpolation and clipped boxes only, got {t}")
+    extra = set(t) - {"type", "keep_ratio", "clip_object_border", "interpolation", "backend", "resize_type"} - _RESIZE_KEYS[kind]
+    if extra:
+        raise ValueError(f"train pipeline: {kind} arguments {sorted(extra)} are not built")
+    try:
+        return ScaleSampler(kind, **{k: t[k] for k in _RESIZE_KEYS[kind] if t.get(k) is not None})
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"train pipeline: {kind}: {e}") from None
+
+
+def _train_flip(t: dict) -> float:
+    prob, direction = t.get("prob"), t.get("direction", "horizontal")
+    if direction != "horizontal":
+        raise ValueError(f"train pipeline: RandomFlip is built for direction='horizontal' only, got {t}")
+    if prob is None:
+        return 0.0
+    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0 <= prob <= 1:
+        raise ValueError(f"train pipeline: RandomFlip prob is one number in [0, 1], got {t}")
+    return float(prob)
+
+
+def resolve_train_pipeline(pipeline) -> dict:
+    """`train_dataloader.dataset.pipeline` -> dict(sampler=ScaleSampler, flip_prob=float): what GpuDetPipeline does for it.
+    Accepted: LoadImageFromFile, LoadAnnotations(with_bbox=True), PackDetInputs, exactly ONE resize stage (Resize /
+    RandomResize with two scales or a ratio_range / RandomChoiceResize, each keep_ratio=True) and at most one
+    RandomFlip(prob=p, direction='horizontal') (absent or prob=None: no flip).  Anything else raises ValueError naming the
+    transform -- a pipeline this path cannot perform must not train as something else."""
+    sampler, flip = None, None
+    for t in pipeline or []:
+        t = _plain(t)
+        kind = t.get("type")
+        if kind in ("LoadImageFromFile", "PackDetInputs"):
+            continue
+        if kind == "LoadAnnotations":
+            if t.get("with_bbox", True) is not True or any(t.get(k) for k in ("with_mask", "with_seg", "with_keypoints")):
+                raise ValueError(f"train pipeline: LoadAnnotations is built for with_bbox=True alone, got {t}")
+        elif kind in _RESIZE_KINDS:
+            if sampler is not None:
+                raise ValueError(f"train pipeline: a second resize stage ({kind}) is not built")
+            sampler = _train_resize(t)
+        elif kind == "RandomFlip":
+            if flip is not None:
+                raise ValueError("train pipeline: a second RandomFlip is not built")
+            flip = _train_flip(t)
+        else:
+            raise ValueError(f"train pipeline: transform {kind!r} is not built")
+    if sampler is None:
+        raise ValueError("train pipeline: no resize stage (Resize, RandomResize or RandomChoiceResize with keep_ratio=True)")
+    return dict(sampler=sampler, flip_prob=0.0 if flip is None else flip)

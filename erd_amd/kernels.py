@@ -1093,6 +1093,26 @@ def resize_normalize_into(src_hwc_u8: Tensor, tables, new_hw, out_slot: Tensor, 
          float(pad_value), _stream())
 
 
+RESIZE_ITEM_BYTES = C.sizeof(_lib.ResizeItem)       # one record {offset, sh, sw, nh, nw, flip} of resize_normalize_batch
+
+
+def resize_normalize_batch(packed_u8: Tensor, n: int, out: Tensor, mean, std, swap_rb: bool, pad_value: float,
+                           table_offset: int = 0) -> None:
+    """resize_normalize_into for a whole batch in ONE launch and without coefficient tables.  packed_u8: one uint8 buffer on the
+    GPU holding `n` records (`_lib.ResizeItem`, at byte table_offset) and the decoded [h,w,3] images at the 16-byte aligned byte
+    offsets the records name (datasets.pack_images builds it); out: [n,3,H,W] fp32.  Slot k equals what resize_normalize_into
+    writes for image k, bit for bit.  Nothing is read back: the caller vouches for the records (the kernel skips one that leaves
+    the buffer)."""
+    _require_gpu(packed_u8, out)
+    assert packed_u8.dtype == torch.uint8 and packed_u8.dim() == 1 and packed_u8.is_contiguous()
+    assert out.dtype == torch.float32 and out.dim() == 4 and out.shape[0] == n and out.shape[1] == 3 and out.is_contiguous()
+    assert table_offset % 8 == 0 and 0 <= table_offset and table_offset + n * RESIZE_ITEM_BYTES <= packed_u8.numel()
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    sd = (C.c_float * 3)(*[float(v) for v in std])
+    call("erd_resize_normalize_batch", _p(packed_u8), packed_u8.numel(), packed_u8.data_ptr() + table_offset, n, _p(out),
+         out.shape[2], out.shape[3], m, sd, int(swap_rb), float(pad_value), _stream())
+
+
 def bn_fold(gamma: Tensor, beta: Tensor, mean: Tensor, var: Tensor, eps: float = 1e-5):
     _require_gpu(gamma)
     scale = torch.empty_like(gamma)

@@ -151,9 +151,11 @@ class CocoTrainData:
     and the GPU image pipeline.  Batches arrive normalised and padded (`preprocessed=True`)."""
 
     def __init__(self, dataset_cfg: dict, batch_size: int, classes=None, scale=(1333, 800), seed: int = 0, rank: int = 0,
-                 world: int = 1, device="cuda", num_workers: int = 0, prefetch_factor: int = 2):
+                 world: int = 1, device="cuda", num_workers: int = 0, prefetch_factor: int = 2, flip_prob: float = 0.5,
+                 scale_sampler=None):
         """num_workers / prefetch_factor: `train_dataloader.num_workers` decoding threads working `prefetch_factor`
-        batches ahead of the training step (0 = decode in the training thread)"""
+        batches ahead of the training step (0 = decode in the training thread); flip_prob / scale_sampler: the RandomFlip
+        and the resize stage of the pipeline (datasets.resolve_train_pipeline; None = the fixed `scale`)"""
         from .datasets import AspectRatioBatchSampler, CocoAnnotations, GpuDetPipeline
         self.num_workers, self.prefetch_factor = int(num_workers), int(prefetch_factor)
         root = dataset_cfg.get("data_root", "")
@@ -162,9 +164,25 @@ class CocoTrainData:
         self.ann = CocoAnnotations(os.path.join(root, dataset_cfg["ann_file"]), classes,
                                    data_prefix=os.path.join(root, (dataset_cfg.get("data_prefix") or {}).get("img", "")),
                                    filter_empty_gt=fc.get("filter_empty_gt", True), min_size=fc.get("min_size", 32))
-        self.pipe = GpuDetPipeline(self.ann, scale=scale, seed=seed, device=device)
+        self.pipe = GpuDetPipeline(self.ann, scale=scale, flip_prob=flip_prob, seed=seed, device=device, scale_sampler=scale_sampler)
         self.bs, self.seed, self.rank, self.world, self.epoch = batch_size, seed, rank, world, 0
         self._sampler_cls = AspectRatioBatchSampler
+
+    @classmethod
+    def from_cfg(cls, cfg, rank: int = 0, world: int = 1, seed: int = 0, device="cuda") -> "CocoTrainData":
+        """the config's `train_dataloader`: batch size, decoding threads and the dataset's pipeline, READ by
+        datasets.resolve_train_pipeline (a transform this path does not perform raises there instead of being skipped)"""
+        from .datasets import resolve_train_pipeline
+        dl = cfg["train_dataloader"]
+        dcfg = dl["dataset"]
+        if dcfg.get("pipeline") is None:
+            raise ValueError("train_dataloader.dataset has no pipeline")
+        pl = resolve_train_pipeline(dcfg["pipeline"])
+        fixed = pl["sampler"].type == "Resize"
+        return cls(dcfg, int(dl["batch_size"]), scale=pl["sampler"].scale if fixed else (1333, 800), seed=seed, rank=rank,
+                   world=world, device=device, num_workers=int(dl.get("num_workers", 0)),
+                   prefetch_factor=int(dl.get("prefetch_factor") or 2), flip_prob=pl["flip_prob"],
+                   scale_sampler=None if fixed else pl["sampler"])
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = epoch
@@ -182,11 +200,12 @@ class CocoTrainData:
         return -(-len(self._indices()) // self.bs)
 
     def __iter__(self):
-        from .datasets import pinned, prefetch_map
+        from .datasets import prefetch_map
         batches = list(self._sampler_cls(self._indices(), self.ann, self.bs))
-        decode = lambda idx: (idx, [pinned(im) for im in self.pipe.decode(idx)])
-        for idx, imgs in prefetch_map(decode, batches, self.num_workers, self.prefetch_factor):
-            x, samples = self.pipe.assemble(idx, imgs)
+        epoch = self.epoch                                        # the draws of a batch decoded ahead belong to ITS epoch
+        decode = lambda idx: (idx, self.pipe.pack(idx, epoch=epoch))       # one page-locked buffer per batch: pixels + records
+        for idx, packed in prefetch_map(decode, batches, self.num_workers, self.prefetch_factor):
+            x, samples = self.pipe.assemble(idx, packed)
             yield dict(inputs=x, data_samples=samples, preprocessed=True)
 
 

@@ -287,6 +287,23 @@ int erd_resize_normalize(const void* src_hwc_u8, int sh, int sw, const int* xofs
                          const int* yofs, const short* ycoef, int nh, int nw, float* out, int H, int W,
                          const float* mean3, const float* std3, int flip, int swap_rb, float pad_value,
                          erd_stream_t stream);
+/* The same pass over a whole batch in ONE launch, with no host-built tables (multi-scale training: every image its own (nh, nw)):
+ * src_u8 is one device buffer of src_bytes bytes that holds the n decoded uint8 [sh][sw][3] images, image k at byte `offset`
+ * (16-byte aligned) of record k; items_dev the n records on the device (they may live in the same buffer).  out is [n][3][H][W];
+ * slot k gets image k resized to (nh, nw) (mirrored when flip), normalised, pad_value elsewhere.  The kernel computes the
+ * coefficients of erd_resize_normalize's tables itself, bit for bit (datasets.linear_coeffs), so slot k equals what
+ * erd_resize_normalize writes for image k.  Rows are stored as float4 when W % 4 == 0 and out is 16-byte aligned, else
+ * element by element.  A record with a non-positive size or one that leaves [0, src_bytes) reads nothing: its slot is padding. */
+typedef struct {
+    int64_t offset;   /* bytes from src_u8 */
+    int sh, sw;       /* decoded size */
+    int nh, nw;       /* resized size, <= (H, W) (the part of it outside the slot is not written) */
+    int flip;
+    int reserved;
+} erd_resize_item;
+int erd_resize_normalize_batch(const void* src_u8, int64_t src_bytes, const erd_resize_item* items_dev, int n, float* out,
+                               int H, int W, const float* mean3, const float* std3, int swap_rb, float pad_value,
+                               erd_stream_t stream);
 
 /* ---- frozen-statistics BN helpers ---------------------------------------------------------- */
 /* scale = gamma*rsqrt(var+eps), shift = beta-mean*scale over n channels (resnet.py:268-300, eval BN) */
