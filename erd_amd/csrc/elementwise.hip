@@ -673,52 +673,42 @@ __global__ __launch_bounds__(256) void level_scale_bwd_kernel(const float* __res
     if (threadIdx.x == 0) atomicAdd(dalphas + s, red[0] + red[1] + red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(256) void sgd_kernel(float4* __restrict__ p, const float4* __restrict__ g,
-                                                  float4* __restrict__ buf, int64_t n4, float lr, float mom, float wd,
-                                                  float gs, int first) {
-    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        float4 pp = p[i];
-        const float4 gg = g[i];
-        float4 d;
-        d.x = gg.x * gs + wd * pp.x; d.y = gg.y * gs + wd * pp.y;
-        d.z = gg.z * gs + wd * pp.z; d.w = gg.w * gs + wd * pp.w;
-        float4 b;
-        if (first) {
-            b = d;
-        } else {
-            b = buf[i];
-            b.x = mom * b.x + d.x; b.y = mom * b.y + d.y; b.z = mom * b.z + d.z; b.w = mom * b.w + d.w;
-        }
-        buf[i] = b;
-        pp.x -= lr * b.x; pp.y -= lr * b.y; pp.z -= lr * b.z; pp.w -= lr * b.w;
-        p[i] = pp;
+// ---- optimizer update with parameter groups, gradient clipping, gradient accumulation ---------------------------------
+// The segment table: entry s covers the elements [seg[s].begin, seg[s + 1].begin) of the flat buffers (absolute offsets; `base`
+// is where p / g / buf start), with the learning-rate multiplier and the ABSOLUTE weight decay of its parameter.  A block's 256
+// float4 are contiguous: the table is searched once per tile for the tile's first element (block-uniform loads), each lane then
+// walks forward to its own segment -- at most a few entries, segments start on multiples of 4 floats (in the trainer: of 64).
+// -> the last entry whose begin <= e0 (the launcher checked seg[0].begin <= base)
+__device__ __forceinline__ int seg_of_tile(const erd_sgd_seg* __restrict__ seg, int nseg, int64_t e0) {
+    int lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (seg[mid].begin <= e0) lo = mid; else hi = mid - 1;
     }
+    return lo;
 }
 
-// ---- optimizer update with parameter groups, gradient clipping, gradient accumulation ---------------------------------
-// sgd_kernel with a segment table: entry s covers the elements [seg[s].begin, seg[s + 1].begin) of the flat buffers (absolute
-// offsets; `base` is where p / g / buf start), with the learning-rate multiplier and the ABSOLUTE weight decay of its parameter.
-// A block's 256 float4 are contiguous: the table is searched once per tile for the tile's first element (block-uniform loads),
-// each lane then walks forward to its own segment -- at most a few entries, segments start on multiples of 4 floats (in the
-// trainer: of 64).  Per element the operations and their order are sgd_kernel's.
-__global__ __launch_bounds__(256) void sgd_groups_kernel(float4* __restrict__ p, const float4* __restrict__ g,
-                                                         float4* __restrict__ buf, int64_t n4, int64_t base,
-                                                         const erd_sgd_seg* __restrict__ seg, int nseg, float lr0, float mom,
-                                                         float gs0, const float* __restrict__ coef, int first) {
-    const float gs = coef ? gs0 * coef[0] : gs0;
+// torch.optim.SGD (momentum, weight decay) over [base, base + 4 * n4) of the flat buffers, a tile of 256 float4 per block and sweep.
+// GROUPS: lr0 * lr_mult and the weight decay of each element's table entry (wd0 is not read), `coef` an optional device float
+// that multiplies gs0 (the clip coefficient); otherwise lr0 and wd0 for every element, and neither table nor coef is touched.
+template <bool GROUPS>
+__global__ __launch_bounds__(256) void sgd_kernel(float4* __restrict__ p, const float4* __restrict__ g,
+                                                  float4* __restrict__ buf, int64_t n4, int64_t base,
+                                                  const erd_sgd_seg* __restrict__ seg, int nseg, float lr0, float mom, float wd0,
+                                                  float gs0, const float* __restrict__ coef, int first) {
+    const float gs = GROUPS && coef ? gs0 * coef[0] : gs0;
     for (int64_t t0 = blockIdx.x * 256ll; t0 < n4; t0 += (int64_t)gridDim.x * 256) {
-        const int64_t e0 = base + t0 * 4;
-        int lo = 0, hi = nseg - 1;               // last entry whose begin <= e0 (the launcher checked seg[0].begin <= base)
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (seg[mid].begin <= e0) lo = mid; else hi = mid - 1;
-        }
+        const int lo = GROUPS ? seg_of_tile(seg, nseg, base + t0 * 4) : 0;
         const int64_t i = t0 + threadIdx.x;
         if (i >= n4) continue;
-        const int64_t e = base + i * 4;
-        int s = lo;
-        while (s + 1 < nseg && seg[s + 1].begin <= e) ++s;
-        const float lr = lr0 * seg[s].lr_mult, wd = seg[s].weight_decay;
+        float lr = lr0, wd = wd0;
+        if (GROUPS) {
+            const int64_t e = base + i * 4;
+            int s = lo;
+            while (s + 1 < nseg && seg[s + 1].begin <= e) ++s;
+            lr = lr0 * seg[s].lr_mult;
+            wd = seg[s].weight_decay;
+        }
         float4 pp = p[i];
         const float4 gg = g[i];
         float4 d;
@@ -738,7 +728,7 @@ __global__ __launch_bounds__(256) void sgd_groups_kernel(float4* __restrict__ p,
 }
 
 // torch.optim.AdamW (decoupled != 0) / torch.optim.Adam (decay joins the gradient) over the same flat buffers with the same segment
-// table, tile search and clip coefficient as sgd_groups_kernel; `seg` null: one learning rate lr0 and one decay wd0.  m / v: first and
+// table, tile search and clip coefficient as sgd_kernel<true>; `seg` null: one learning rate lr0 and one decay wd0.  m / v: first and
 // second moment.  omb1 = 1 - beta1 and omb2 = 1 - beta2 are rounded from the host's doubles (1 - float(0.999) is 1.3e-5 off 0.001);
 // ib1 = 1 / (1 - beta1^t), isb2 = 1 / sqrt(1 - beta2^t).  28 B per element, no reuse: an HBM pass like the SGD one.  Divide and
 // square root are the compiler's correctly rounded ones, the fused multiply-adds are written out (the bits do not hang on what
@@ -758,15 +748,7 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(float4* __restrict__ p
                                                           float gs0, const float* __restrict__ coef, int decoupled) {
     const float gs = coef ? gs0 * coef[0] : gs0;
     for (int64_t t0 = blockIdx.x * 256ll; t0 < n4; t0 += (int64_t)gridDim.x * 256) {
-        int lo = 0;
-        if (seg) {                               // last entry whose begin <= the tile's first element, as in sgd_groups_kernel
-            const int64_t e0 = base + t0 * 4;
-            int hi = nseg - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (seg[mid].begin <= e0) lo = mid; else hi = mid - 1;
-            }
-        }
+        const int lo = seg ? seg_of_tile(seg, nseg, base + t0 * 4) : 0;
         const int64_t i = t0 + threadIdx.x;
         if (i >= n4) continue;
         float lr = lr0, wd = wd0;
@@ -1278,9 +1260,10 @@ extern "C" int erd_sgd_momentum(float* p, const float* g, float* buf, int64_t n,
                                 float weight_decay, float grad_scale, int first_step, erd_stream_t stream) {
     ERD_REQUIRE(p && g && buf && n % 4 == 0, "sgd: bad args (n must be a multiple of 4)");
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(buf),
-                       n / 4, lr, momentum, weight_decay, grad_scale, first_step);
+    hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(buf), n / 4,
+                       (int64_t)0, (const erd_sgd_seg*)nullptr, 0, lr, momentum, weight_decay, grad_scale, (const float*)nullptr,
+                       first_step);
     return erd::check_launch("sgd");
 }
 
@@ -1319,9 +1302,9 @@ extern "C" int erd_sgd_momentum_groups(float* p, const float* g, float* buf, int
     ERD_REQUIRE(seg0 >= 0 && nseg >= 1 && seg0_begin <= base && base + n <= seg_end, "sgd_groups: segments [%lld, %lld) do not cover "
                 "the range [%lld, %lld)", (long long)seg0_begin, (long long)seg_end, (long long)base, (long long)(base + n));
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sgd_groups_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(buf), n / 4, base,
-                       table_dev + seg0, nseg, lr, momentum, grad_scale, clip_coef, first_step);
+                       table_dev + seg0, nseg, lr, momentum, 0.f, grad_scale, clip_coef, first_step);
     return erd::check_launch("sgd_groups");
 }
 

@@ -15,7 +15,7 @@ re-designed for one process per MI355X:
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import os
 import time
@@ -315,6 +315,15 @@ class TeacherGraphs:
         return out
 
 
+class _Plan(NamedTuple):
+    """what the update of one step does, fixed before the step's backward pass (ERDTrainer._plan_step)"""
+    lr: float
+    t: int                # AdamW's / Adam's `step`: updates planned so far, this one included
+    micro_first: bool     # first micro-step of its accumulation window
+    close: bool           # the step closes its window: the update is applied
+    m: int                # micro-steps in the window so far
+
+
 class ERDTrainer:
     """One optimisation step of the ERD incremental detector per call (teacher fwd -> ERS -> student fwd ->
     losses -> backward -> gradient mean over ranks -> SGD)."""
@@ -326,12 +335,13 @@ class ERDTrainer:
                  paramwise_cfg: Optional[dict] = None, clip_grad: Optional[dict] = None, accumulative_counts: int = 1,
                  optimizer: Optional[dict] = None):
         """paramwise_cfg / clip_grad / accumulative_counts: the `optim_wrapper` keys of those names (mmengine's OptimWrapper and
-        DefaultOptimWrapperConstructor; optim_cfg.py).  Without them the update is ONE scalar learning rate and weight decay
-        (erd_sgd_momentum) exactly as before; with any of them see _update_bucket_ext / _apply_pending_ext.
+        DefaultOptimWrapperConstructor; optim_cfg.py).  Every update takes ONE path (_plan_step -> _update_bucket / _apply_pending
+        -> _update_range); without the options it runs at their neutral values: no segment table (erd_sgd_momentum with one scalar
+        learning rate and weight decay), no clip coefficient, no accumulator, a window of one micro-step that always closes.
         optimizer: `optim_wrapper.optimizer`.  None or type='SGD': the SGD update from `lr`, `momentum`, `weight_decay` above.
         type='AdamW' / 'Adam' (optim_cfg.check_optimizer): lr, betas, eps and weight_decay come from THIS dict (torch's defaults
-        where it is silent) and every launch site of the SGD kernels launches erd_adam_groups instead -- same buckets, grad
-        scale, clip coefficient, accumulation window and derived-state refresh."""
+        where it is silent) and _launch_update launches erd_adam_groups instead of the SGD kernel -- same buckets, grad scale,
+        clip coefficient, accumulation window and derived-state refresh."""
         self.model = model
         self.opt = OC.check_optimizer(optimizer)
         self.adam = self.opt["type"] in OC.ADAM_TYPES
@@ -361,15 +371,15 @@ class ERDTrainer:
         self.epoch_factor = 1.0              # MultiStepLR factor of the current epoch (set by the runner)
         self.lr_factor = None                # optional callable iter -> factor replacing the built-in warm-up
         self.last_lr = self.base_lr
-        self._pending_lr = self.base_lr
         self._first = True
         self._pending = False                # an un-applied gradient sits in flat.grad
         # AdamW / Adam: the first moment lives in flat.momentum, the second in one more flat buffer (not allocated for SGD);
-        # `_t` counts the updates planned so far -- one per CLOSED window, not per micro-step -- and `_pending_t` is the count of
-        # the update being issued / pending, fixed with `_pending_lr` when the step is planned: every bucket of one step takes
-        # the same bias corrections although the update is deferred behind the next teacher forward
+        # `_t` counts the updates planned so far -- one per CLOSED window, not per micro-step.  `_plan` holds what the update being
+        # issued / pending does (learning rate, update count, window state), fixed when the step is planned: every bucket of one
+        # step takes the same learning rate and bias corrections although the update is deferred behind the next teacher forward
         self.exp_avg_sq = torch.zeros_like(self.flat.momentum) if self.adam else None
-        self._t = self._pending_t = 0
+        self._t = 0
+        self._plan = _Plan(lr=self.base_lr, t=0, micro_first=True, close=True, m=1)
         # optim_wrapper options.  `resolved`: per-parameter lr multiplier / weight decay (model.parameters() order); `_table`: its
         # device form, one segment per flat parameter (also built for clipping alone: the coefficient enters through the same
         # kernel); `_acc`: the accumulation window's gradient sum (backward kernels need flat.grad zero at the start of every
@@ -384,9 +394,7 @@ class ERDTrainer:
             self._table = K.SgdSegTable(self.flat.offsets + [self.flat.total], [r["lr_mult"] for r in rows],
                                         [r["weight_decay"] for r in rows], dev)
         self._acc = torch.zeros_like(self.flat.grad) if self.accum > 1 else None
-        self._ext = self._table is not None or self._acc is not None
         self._window = 0                     # micro-steps whose gradient is in (or on its way into) `_acc` and not applied yet
-        self._micro_first, self._close, self._m = True, True, 1      # of the step being issued / pending (_plan_step)
         self._norm_ws = self._norm_out = None
         self._teacher_ahead = None           # (inputs, TeacherOut) of the following step (train_step(next_batch=...))
         self.prefold = Fn.BnPrefold(model) if os.environ.get("ERD_BN_PREFOLD", "1") != "0" else None
@@ -456,52 +464,27 @@ class ERDTrainer:
         parts = name.split(".")
         return ".".join(parts[:3]) if parts[0] == "backbone" and len(parts) > 3 else parts[0]
 
-    def _update_bucket(self, b: int) -> None:
-        """BucketedGradSync.on_bucket: the summed gradient of bucket b is final and every launch that reads the bucket's
-        weights / folded scales / prepared buffers is queued ahead of the current (update) stream"""
-        if self._ext:
-            return self._update_bucket_ext(b)
-        s, e, _ = self.flat.buckets[b]
-        if self.adam:
-            self._adam_update(s, e, self.flat.grad, 1.0 / self.world)
-        else:
-            K.sgd_momentum_(self.flat.data[s:e], self.flat.grad[s:e], self.flat.momentum[s:e], self._pending_lr, self.momentum,
-                            self.weight_decay, 1.0 / self.world, self._first)
-        self.flat.refresh_shadow(b)
-        self.prefold.run_group(b)
-        if self.prefold.valid[0]:
-            self.prep.run_group(b)
-        else:
-            self.prep.invalidate()
+    @property
+    def _pending_lr(self) -> float:
+        """the learning rate of the update being issued / pending (trainer snapshots outside this module read it)"""
+        return self._plan.lr
 
-    def _adam_update(self, s: int, e: int, g: Tensor, scale: float) -> None:
-        """AdamW / Adam on [s, e) of the flat buffers from the gradient buffer g, one launch: the learning rate and the update
-        count of the step as planned, the segment table and the clip coefficient when the trainer has them"""
-        K.adam_groups_(self.flat.data[s:e], g[s:e], self.flat.momentum[s:e], self.exp_avg_sq[s:e], s, self._table, self._pending_lr,
-                       self.weight_decay, self.opt["betas"], self.opt["eps"], self._pending_t, scale, self.opt["type"] == "AdamW",
-                       None if self.clip is None else self._norm_out[1:2])
-
-    def _count_update(self) -> None:
-        """one more update is planned (a window closes): AdamW's / Adam's `step`"""
-        self._t += 1
-        self._pending_t = self._t
-
-    # -- the update with optim_wrapper options (paramwise_cfg, clip_grad, accumulative_counts) ------------------------------
+    # -- the update: SGD / AdamW / Adam with the optim_wrapper options (paramwise_cfg, clip_grad, accumulative_counts) ----------------
     def _plan_step(self, log_vars) -> None:
-        """fixes what the update of the step being issued does BEFORE its backward pass (per-bucket updates start inside it):
-        first micro-step of a window or not, closing the window or not (mmengine: (iter + 1) % accumulative_counts == 0),
-        micro-steps in the window; with clipping a closing step logs `grad_norm`, a device float written by the update"""
-        if not self._ext:
-            self._count_update()
-            return
-        self._micro_first = self._window == 0
+        """fixes what the update of the step being issued does BEFORE its backward pass (per-bucket updates start inside it): the
+        learning rate, first micro-step of a window or not, closing the window or not (mmengine: (iter + 1) %
+        accumulative_counts == 0), micro-steps in the window, the update count of a closing step; with clipping a closing step
+        logs `grad_norm`, a device float written by the update"""
+        self.last_lr = self.lr_at(self.iter, self.epoch_factor)
+        micro_first = self._window == 0
         self._window += 1
-        self._close, self._m = OC.should_update(self.iter, self.accum), self._window
-        if self._close:
+        close, m = OC.should_update(self.iter, self.accum), self._window
+        if close:
             self._window = 0
-            self._count_update()
-            if self.clip is not None:
-                log_vars["grad_norm"] = self._new_norm_out()[0]
+            self._t += 1
+        self._plan = _Plan(self.last_lr, self._t, micro_first, close, m)
+        if close and self.clip is not None:
+            log_vars["grad_norm"] = self._new_norm_out()[0]
 
     def _new_norm_out(self) -> Tensor:
         """(total_norm, coefficient) of one update: a buffer per update, the log keeps reading the previous ones"""
@@ -510,21 +493,29 @@ class ERDTrainer:
             self._norm_out.record_stream(self.sync.stream)
         return self._norm_out
 
-    def _update_range(self, b: Optional[int]) -> None:
-        """SGD on bucket b's slice (None: the whole buffers), then the derived state of that range: bf16 shadow, BN folds,
-        prepared weights.  Reads the window's sum when gradients are accumulated; grad_scale = 1 / (ranks * micro-steps)"""
-        s, e = (0, self.flat.total) if b is None else self.flat.buckets[b][:2]
-        g = self.flat.grad if self._acc is None else self._acc
-        scale = 1.0 / (self.world * self._m)
+    def _launch_update(self, s: int, e: int) -> None:
+        """one launch over [s, e) of the flat buffers: AdamW / Adam, SGD with the segment table, or SGD with one learning rate and
+        weight decay.  Reads the window's sum when gradients are accumulated; grad_scale = 1 / (ranks * micro-steps); the clip
+        coefficient enters through the table kernels"""
+        plan, flat = self._plan, self.flat
+        g = flat.grad if self._acc is None else self._acc
+        scale = 1.0 / (self.world * plan.m)
+        coef = None if self.clip is None else self._norm_out[1:2]
         if self.adam:
-            self._adam_update(s, e, g, scale)
+            K.adam_groups_(flat.data[s:e], g[s:e], flat.momentum[s:e], self.exp_avg_sq[s:e], s, self._table, plan.lr,
+                           self.weight_decay, self.opt["betas"], self.opt["eps"], plan.t, scale, self.opt["type"] == "AdamW", coef)
         elif self._table is None:
-            K.sgd_momentum_(self.flat.data[s:e], g[s:e], self.flat.momentum[s:e], self._pending_lr, self.momentum,
-                            self.weight_decay, scale, self._first)
+            K.sgd_momentum_(flat.data[s:e], g[s:e], flat.momentum[s:e], plan.lr, self.momentum, self.weight_decay, scale,
+                            self._first)
         else:
-            K.sgd_momentum_groups_(self.flat.data[s:e], g[s:e], self.flat.momentum[s:e], s, self._table, self._pending_lr,
-                                   self.momentum, scale, self._first, None if self.clip is None else self._norm_out[1:2])
-        self.flat.refresh_shadow(b)
+            K.sgd_momentum_groups_(flat.data[s:e], g[s:e], flat.momentum[s:e], s, self._table, plan.lr, self.momentum, scale,
+                                   self._first, coef)
+
+    def _refresh_derived(self, b: Optional[int]) -> None:
+        """refreshes what the coming step reads instead of the weights of bucket b (None: of all buckets): the folded scales and
+        shifts of every trainable BN of the student (one launch), then the prepared weights -- transposed weights, Winograd weight
+        images -- that are built from them (two launches).  When the BN folds are not valid (no prefold, or its device table went
+        stale) the prepared weights are invalidated instead, and the convolutions prepare their weights per use"""
         if self.prefold is not None:
             self.prefold.run() if b is None else self.prefold.run_group(b)
         if self.prep is not None:
@@ -533,23 +524,33 @@ class ERDTrainer:
             else:
                 self.prep.invalidate()
 
+    def _update_range(self, b: Optional[int]) -> None:
+        """the update on bucket b's slice (None: the whole buffers), then the derived state of that range: bf16 shadow, BN folds,
+        prepared weights"""
+        s, e = (0, self.flat.total) if b is None else self.flat.buckets[b][:2]
+        self._launch_update(s, e)
+        self.flat.refresh_shadow(b)
+        self._refresh_derived(b)
+
     def _apply_window(self) -> None:
-        """the update over the whole buffers on the current stream: [norm -> coefficient ->] SGD -> derived state"""
+        """the update over the whole buffers on the current stream: [norm -> coefficient ->] update -> derived state"""
         if self.clip is not None:
             slot = self._norm_ws[:K._lib.ERD_SQNORM_PARTS]
             K.grad_sqnorm_into(self.flat.grad if self._acc is None else self._acc, slot)
-            K.clip_coef_(slot, 1.0 / (self.world * self._m), self.clip["max_norm"], self._norm_out)
+            K.clip_coef_(slot, 1.0 / (self.world * self._plan.m), self.clip["max_norm"], self._norm_out)
         self._update_range(None)
 
-    def _update_bucket_ext(self, b: int) -> None:
-        """_update_bucket with options.  Accumulation: the bucket's summed gradient joins the window; a step that does not close
-        the window ends here.  Clipping: the coefficient needs EVERY bucket, so a bucket only queues the sum of squares of its
-        slice (behind its all-reduce, on the update stream); the last bucket -- released when the backward pass has ended, so
-        every launch that reads any weight is queued ahead -- adds the finalize and then updates all buckets."""
+    def _update_bucket(self, b: int) -> None:
+        """BucketedGradSync.on_bucket: the summed gradient of bucket b is final and every launch that reads the bucket's
+        weights / folded scales / prepared buffers is queued ahead of the current (update) stream.
+        Accumulation: the bucket's summed gradient joins the window; a step that does not close the window ends here.
+        Clipping: the coefficient needs EVERY bucket, so a bucket only queues the sum of squares of its slice (behind its
+        all-reduce, on the update stream); the last bucket -- released when the backward pass has ended, so every launch that
+        reads any weight is queued ahead -- adds the finalize and then updates all buckets."""
         s, e, _ = self.flat.buckets[b]
         if self._acc is not None:
-            K.grad_accumulate_(self._acc[s:e], self.flat.grad[s:e], self._micro_first)
-        if not self._close:
+            K.grad_accumulate_(self._acc[s:e], self.flat.grad[s:e], self._plan.micro_first)
+        if not self._plan.close:
             return
         if self.clip is None:
             self._update_range(b)
@@ -558,59 +559,34 @@ class ERDTrainer:
         g = self.flat.grad if self._acc is None else self._acc
         K.grad_sqnorm_into(g[s:e], self._norm_ws[b * P:(b + 1) * P])
         if b == len(self.flat.buckets) - 1:
-            K.clip_coef_(self._norm_ws, 1.0 / (self.world * self._m), self.clip["max_norm"], self._norm_out)
+            K.clip_coef_(self._norm_ws, 1.0 / (self.world * self._plan.m), self.clip["max_norm"], self._norm_out)
             for j in range(len(self.flat.buckets)):
                 self._update_range(j)
 
-    def _apply_pending_ext(self) -> None:
+    def _apply_pending(self) -> None:
+        """wait for the bucket all-reduces of the previous backward, then the update over the whole buffers -- or, with the
+        per-bucket update, release the buckets that are left (the tail) and join the update stream."""
+        if not self._pending:
+            return
         if self.sync is not None:
             self.sync.wait()
         if not self.bucket_update:
             if self._acc is not None:
-                K.grad_accumulate_(self._acc, self.flat.grad, self._micro_first)
-            if self._close:
+                K.grad_accumulate_(self._acc, self.flat.grad, self._plan.micro_first)
+            if self._plan.close:
                 self._apply_window()
-        if self._close:
+        if self._plan.close:
             self._first = False
         self._pending = False
-
-    def _apply_pending(self) -> None:
-        """wait for the bucket all-reduces of the previous backward, then ONE fused SGD launch -- or, with the per-bucket
-        update, release the buckets that are left (the tail) and join the update stream."""
-        if not self._pending:
-            return
-        if self._ext:
-            return self._apply_pending_ext()
-        if self.bucket_update:
-            self.sync.wait()
-            self._first = False
-            self._pending = False
-            return
-        if self.sync is not None:
-            self.sync.wait()
-        if self.adam:
-            self._adam_update(0, self.flat.total, self.flat.grad, 1.0 / self.world)
-        else:
-            K.sgd_momentum_(self.flat.data, self.flat.grad, self.flat.momentum, self._pending_lr, self.momentum,
-                            self.weight_decay, 1.0 / self.world, self._first)
-        self._first = False
-        self._pending = False
-        self.flat.refresh_shadow()
-        if self.prefold is not None:
-            self.prefold.run()               # every trainable BN of the student folded for the coming step, one launch
-        if self.prep is not None:            # transposed weights / Winograd weight images of the coming step, two launches
-            if self.prefold is not None and self.prefold.valid[0]:
-                self.prep.run()
-            else:
-                self.prep.invalidate()
 
     def flush(self, close_window: bool = True) -> None:
         """apply what is pending.  With gradient accumulation this also closes the window: a partial window of m micro-steps is
         applied with 1 / m (close_window=False only settles the last step: the runner's log read-back)"""
         self._apply_pending()
-        if close_window and self._ext and self._window > 0:
-            self._m, self._window = self._window, 0
-            self._count_update()
+        if close_window and self._window > 0:
+            self._t += 1
+            self._plan = self._plan._replace(t=self._t, close=True, m=self._window)
+            self._window = 0
             if self.clip is not None:
                 self._new_norm_out()
             self._apply_window()
@@ -716,7 +692,7 @@ class ERDTrainer:
                 _storage_view(self.flat.momentum, off, p).copy_(st["exp_avg"].to(self.device))
                 _storage_view(self.exp_avg_sq, off, p).copy_(st["exp_avg_sq"].to(self.device))
                 loaded += 1
-            self._t = self._pending_t = int(steps.pop()) if steps else 0
+            self._t = int(steps.pop()) if steps else 0
             self._first = loaded == 0
             return
         for i, st in sd.get("state", {}).items():
@@ -789,18 +765,12 @@ class ERDTrainer:
                     # Winograd weight images) but they only vouch for the parameters once the batched preparation has run -- until round
                     # 6 the capture therefore recorded the ~250 per-use preparation launches of a step (42 bn_fold, 45 wino_weight_x3,
                     # 58 weight_transpose, 73 split3, ...: `profiles/r06_graph_timelines.txt`) and replayed them every step, which is
-                    # most of why the replay was slower than eager.  Prepare now, as _apply_pending does after every update: the
+                    # most of why the replay was slower than eager.  Prepare now, as _update_range does after every update: the
                     # captured step reads the prepared buffers by address.
                     # Twice, with a warm-up pass in between: the input-gradient convolutions' Winograd / limb images are derived from
                     # the PREPARED transposed weights, so their recipes can only be registered by a pass that already found those.
                     for rnd in range(2):
-                        if self.prefold is not None:
-                            self.prefold.run()
-                        if self.prep is not None:
-                            if self.prefold is not None and self.prefold.valid[0]:
-                                self.prep.run()
-                            else:
-                                self.prep.invalidate()
+                        self._refresh_derived(None)
                         if rnd == 0:
                             self._graph_body(st)
                 s.synchronize()
@@ -864,7 +834,6 @@ class ERDTrainer:
             log_vars = self._train_step_graph(inputs, data_samples)
             if log_vars is not None:
                 self._pending = True
-                self._pending_lr = self.last_lr = self.lr_at(self.iter, self.epoch_factor)
                 self._plan_step(log_vars)
                 self.iter += 1
                 return log_vars
@@ -914,8 +883,7 @@ class ERDTrainer:
             self.side.wait_stream(cur)
             with torch.cuda.stream(self.side), torch.no_grad():
                 self._teacher_ahead = (next_batch[0], self._teacher(next_batch[0], next_batch[1], self.iter + 1))
-        self._pending_lr = self.last_lr = self.lr_at(self.iter, self.epoch_factor)      # (per-bucket updates start inside backward)
-        self._plan_step(log_vars)
+        self._plan_step(log_vars)              # (before the backward pass: per-bucket updates start inside it)
         if self.sync is not None:
             self.sync.arm()
         total.backward()

@@ -137,6 +137,34 @@ def test_sgd_momentum_groups_with_unit_multipliers_is_bit_equal_to_sgd_momentum(
         K.SgdSegTable([0, 6, 64], [1.0, 1.0], [0.0, 0.0], "cuda")
 
 
+@pytest.mark.parametrize("n", [4, 4 * 257, 4 * (4096 * 256 + 257)])
+def test_sgd_momentum_at_the_tile_edges(K, n):
+    """the shapes at which a kernel that walks tiles of 256 float4 can go wrong: one lane; one full tile plus one lane (the guard
+    of the ragged tile); one full sweep of the 4096-block grid cap, then a second sweep with a ragged last tile.  3 steps of
+    sgd_momentum_ stay within 1e-6 of the host update (the bound test_gpu_kernels.py::test_level_scale_colsum_sgd holds this
+    entry to) and are bit-equal to sgd_momentum_groups_ with a unit table of 64-aligned segments of mixed sizes."""
+    offs = [0]
+    while offs[-1] < n:
+        offs.append(offs[-1] + ALIGN * (1, 3, 16, 1, 33, 4097, 2)[(len(offs) - 1) % 7])
+    lr, mom, wd, gs = 0.02, 0.9, 1e-4, 0.5
+    table = K.SgdSegTable(offs, [1.0] * (len(offs) - 1), [wd] * (len(offs) - 1), "cuda")
+    p = G.randn(87, n)
+    pa, ba = p.cuda(), torch.zeros(n, device="cuda")
+    pb, bb = p.cuda(), torch.zeros(n, device="cuda")
+    ps, bufs = [p], None
+    for it in range(3):
+        g = G.randn(88 + it, n)
+        gd = g.cuda()
+        K.sgd_momentum_(pa, gd, ba, lr * (it + 1), mom, wd, gs, it == 0)
+        K.sgd_momentum_groups_(pb, gd, bb, 0, table, lr * (it + 1), mom, gs, it == 0)
+        ps, bufs, _ = host_update(ps, [g], bufs, [lr * (it + 1)], [wd], mom, gs)
+    torch.cuda.synchronize()
+    ep, eb = relerr(pa.cpu(), ps[0]), relerr(ba.cpu(), bufs[0])
+    print(f"sgd n={n}: relerr params {ep:.3e} momenta {eb:.3e}")
+    assert ep < 1e-6 and eb < 1e-6
+    assert torch.equal(pa, pb) and torch.equal(ba, bb)
+
+
 @pytest.mark.parametrize("n", [4, 1000004, 32 << 20])
 @pytest.mark.parametrize("nb", [1, 7])
 def test_grad_sqnorm_and_clip_coef_follow_the_fp64_norm(K, n, nb):
@@ -328,6 +356,154 @@ def test_unit_custom_key_leaves_the_weights_of_a_plain_trainer(monkeypatch):
     assert len(names) > 50
     assert not [n for n in names if not torch.equal(got[0][n], got[1][n])]
     assert not torch.equal(got[0]["bbox_head.gfl_cls.weight"], ssd["bbox_head.gfl_cls.weight"])
+
+
+# the update census: which entries of the library one optimisation step calls for its update, with which ranges, in which order
+UPDATES = ("erd_sgd_momentum", "erd_sgd_momentum_groups", "erd_adam_groups")
+DERIVED = ("erd_bn_fold_batch", "erd_weight_prep_batch")       # BnPrefold.run / run_group, ParamPrep.run / run_group
+CENSUS = UPDATES + DERIVED + ("erd_grad_sqnorm", "erd_clip_coef", "erd_grad_accumulate")
+CENSUS_CASES = {                # trainer options, ERD_BUCKET_UPDATE, train_step calls
+    "plain-whole": (dict(), "0", 3),
+    "plain-buckets": (dict(), "1", 3),
+    "table-whole": (dict(paramwise_cfg=TABLE_CFG), "0", 3),
+    "table-buckets": (dict(paramwise_cfg=TABLE_CFG), "1", 3),
+    "table-clip-buckets": (dict(paramwise_cfg=TABLE_CFG, clip_grad=dict(max_norm=35, norm_type=2)), "1", 3),
+    "table-clip-whole": (dict(paramwise_cfg=TABLE_CFG, clip_grad=dict(max_norm=35, norm_type=2)), "0", 3),
+    "accumulate-whole": (dict(accumulative_counts=2), "0", 5),
+    "accumulate-buckets": (dict(accumulative_counts=2), "1", 5),
+    "adamw-whole": (dict(optimizer=dict(type='AdamW', lr=1e-3)), "0", 3),
+    "adamw-buckets": (dict(optimizer=dict(type='AdamW', lr=1e-3)), "1", 3),
+}
+
+
+@pytest.fixture(scope="module")
+def census_inputs():
+    return f7_state_dicts(), _batches((0, 1, 2))
+
+
+@pytest.mark.parametrize("case", sorted(CENSUS_CASES))
+def test_update_census(K, case, census_inputs, monkeypatch):
+    """every call the trainer makes into the library goes through kernels.call: recorded for `steps` train_step +
+    flush(close_window=False) and a closing flush(), the update-path entries of each step are exactly
+      whole buffers: [erd_grad_accumulate] then, when the step closes its window, [erd_grad_sqnorm, erd_clip_coef,] ONE update launch
+                     over flat.total;
+      per bucket:    for each bucket in order [erd_grad_accumulate,] and, closing, the update launch over the bucket -- with clipping
+                     erd_grad_sqnorm per bucket instead, then one erd_clip_coef, then the update launches of all buckets in order;
+    each update launch is followed at once by the derived state of ITS range (the BN folds of that bucket / of all, then at most two
+    weight preparation launches of that bucket / of all) and a step that closes no window issues none."""
+    from erd_amd.engine import ERDTrainer
+    opts, bucket_update, steps = CENSUS_CASES[case]
+    (tsd, ssd), batches = census_inputs
+    monkeypatch.setenv("ERD_BUCKET_UPDATE", bucket_update)
+    log, cur = [], {}
+    real = K.call
+    ptr = lambda a: getattr(a, "value", a)
+
+    def owner(name, args):
+        """the range a derived-state launch works on, from the device table it is given: a bucket, or None for everything"""
+        tr, t = cur["tr"], ptr(args[0])
+        if name == "erd_bn_fold_batch":
+            if t == tr.prefold.table.data_ptr():
+                return None
+            return next(g for g, ent in tr.prefold.gtables.items() if ent[0].data_ptr() == t)
+        if any(tab[0].data_ptr() == t for tab in (tr.prep._tables or [])):
+            return None
+        return next(g for g, tabs in tr.prep._gtables.items() if any(tab[0].data_ptr() == t for tab in tabs))
+
+    def recorder(name, *args):
+        if name in CENSUS and "tr" in cur:
+            log.append((name, args, owner(name, args) if name in DERIVED else None))
+        return real(name, *args)
+
+    monkeypatch.setattr(K, "call", recorder)
+    model = build_erd(tsd, ssd)
+    tr = ERDTrainer(model, lr=0.02, batch_size_per_gpu=2, auto_scale_lr=False, warmup_iters=0, bucket_mb=1, **opts)
+    cur["tr"] = tr
+    buckets = [(s, e) for s, e, _ in tr.flat.buckets]
+    nb, total = len(buckets), tr.flat.total
+    assert tr.bucket_update == (bucket_update == "1") and nb >= 4
+    accum, clip, adam = opts.get("accumulative_counts", 1), "clip_grad" in opts, "optimizer" in opts
+    assert not adam or tuple(tr.opt["betas"]) == (0.9, 0.999)
+    kind = "erd_adam_groups" if adam else "erd_sgd_momentum_groups" if "paramwise_cfg" in opts else "erd_sgd_momentum"
+    ranges = list(enumerate(buckets)) if tr.bucket_update else [(None, (0, total))]
+    folded = lambda b: bool(tr.prefold.bns) if b is None else b in tr.prefold.gtables
+
+    def token(name, args):
+        """(entry, base or None, n, what else the table of the issue pins)"""
+        if name == "erd_sgd_momentum":
+            return (name, None, args[3])
+        if name == "erd_sgd_momentum_groups":
+            return (name, args[3], args[4])
+        if name == "erd_adam_groups":
+            return (name, args[4], args[5], args[16], args[17])
+        if name == "erd_grad_accumulate":
+            return (name, args[2], args[3])
+        if name == "erd_grad_sqnorm":
+            return (name, args[1])
+        return (name,)
+
+    def update_token(s, e, t):
+        if kind == "erd_sgd_momentum":
+            return (kind, None, e - s)
+        if kind == "erd_sgd_momentum_groups":
+            return (kind, s, e - s)
+        # `step` does not cross the C ABI: the entry takes the two bias corrections of update t, 1 / (1 - beta1^t) and
+        # 1 / sqrt(1 - beta2^t) in double, written out here (torch's defaults: betas 0.9, 0.999)
+        return (kind, s, e - s, 1.0 / (1.0 - 0.9 ** t), 1.0 / (1.0 - 0.999 ** t) ** 0.5)
+
+    def check(entries, micro_first, close, t, ranges, what):
+        want = []
+        for b, (s, e) in ranges:
+            if accum > 1 and micro_first is not None:
+                want.append(("erd_grad_accumulate", e - s, 1 if micro_first else 0))
+            if close and clip:
+                want.append(("erd_grad_sqnorm", e - s))
+            elif close:
+                want.append(update_token(s, e, t))
+        if close and clip:
+            want.append(("erd_clip_coef",))
+            want += [update_token(s, e, t) for _, (s, e) in ranges]
+        got = [token(n, a) for n, a, _ in entries if n not in DERIVED]
+        assert got == want, (what, got, want)
+        # the derived state: right behind the update launch of its range, the folds first
+        runs, run = [], None
+        for n, _, o in entries:
+            if n in UPDATES:
+                run = []
+                runs.append(run)
+            elif n in DERIVED:
+                assert run is not None, (what, "derived state without an update launch right in front of it", n)
+                run.append((n, o))
+            else:
+                run = None
+        assert len(runs) == (len(ranges) if close else 0), what
+        for (b, _), run in zip(ranges, runs):
+            assert [o for _, o in run] == [b] * len(run), (what, b, run)
+            names = [n for n, _ in run]
+            nfold = names.count("erd_bn_fold_batch")
+            assert names == ["erd_bn_fold_batch"] * nfold + ["erd_weight_prep_batch"] * (len(names) - nfold), (what, b, names)
+            assert nfold == (1 if folded(b) else 0) and len(names) - nfold <= 2, (what, b, names)
+            if t >= 2:                   # (from the second update on every range has registered its prepared weights)
+                assert len(names) - nfold >= 1, (what, b, names)
+
+    t = window = 0
+    for it in range(steps):
+        del log[:]
+        tr.train_step(*batches[it % len(batches)])
+        tr.flush(close_window=False)
+        micro_first, window = window == 0, window + 1
+        close = (it + 1) % accum == 0
+        if close:
+            t, window = t + 1, 0
+        check(list(log), micro_first, close, t, ranges, f"{case} step {it + 1}")
+    del log[:]
+    tr.flush()
+    if window:                           # the partial window: ONE update over the whole buffers, nothing left to accumulate
+        t += 1
+    check(list(log), None, window > 0, t, [(None, (0, total))], f"{case} closing flush")
+    torch.cuda.synchronize()
+    assert tr._t == t and not tr._first
+    assert (tr._acc is not None) == (accum > 1) and (tr.exp_avg_sq is not None) == adam
 
 
 def test_runner_example_config_logs_grad_norm_checkpoints_groups_and_resumes(tmp_path):

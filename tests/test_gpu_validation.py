@@ -73,7 +73,7 @@ def _trainer_state(r):
     for k, v in r.model.state_dict().items():
         snap["model." + k] = v
     snap = {k: v.detach().clone() for k, v in snap.items()}
-    meta = dict(iter=t.iter, epoch=r.epoch, lr=t.last_lr, pending_lr=t._pending_lr, epoch_factor=t.epoch_factor,
+    meta = dict(iter=t.iter, epoch=r.epoch, lr=t.last_lr, plan=t._plan, epoch_factor=t.epoch_factor,
                 pending=t._pending, first=t._first, ahead=t._teacher_ahead is None,
                 prep_stamp=None if t.prep is None else t.prep.stamp, prefold_valid=None if t.prefold is None else list(t.prefold.valid),
                 training=r.model.training, recipes=None if t.prep is None else sorted(map(str, t.prep.recipes)))

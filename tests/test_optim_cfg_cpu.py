@@ -129,10 +129,11 @@ def test_example_config_sets_the_three_keys():
 
 
 def test_update_kernels_in_the_isa(tmp_path):
-    """what the compiler makes of the new kernels (hipcc cross-compiles without a GPU): no scratch; 16-byte loads and stores; the
-    element arithmetic of sgd_groups_kernel is sgd_kernel's (the same packed multiplies and fused multiply-adds: with multipliers
-    1 the two give the same bits, asserted on the GPU); the norm kernels accumulate in fp64 and use no atomics (bitwise
-    repeatable); the table search of sgd_groups_kernel runs on scalar loads."""
+    """what the compiler makes of the update kernels (hipcc cross-compiles without a GPU): no scratch; 16-byte loads and stores; the
+    two instantiations of sgd_kernel (<false>: one learning rate and decay, <true>: the segment table) carry the same element
+    arithmetic (the same packed multiplies and fused multiply-adds: with multipliers 1 the two give the same bits, asserted on
+    the GPU); the norm kernels accumulate in fp64 and use no atomics (bitwise repeatable); the table search of sgd_kernel<true>
+    runs on scalar loads and sgd_kernel<false> loads nothing from a table."""
     import re
     import shutil
     import subprocess
@@ -146,20 +147,26 @@ def test_update_kernels_in_the_isa(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     s = open(out).read()
     bodies = {}
+    plain, groups = "sgd_kernelILb0E", "sgd_kernelILb1E"          # (the mangled template arguments <false> / <true>)
     for m in re.finditer(r"^(_Z\S+):[^\n]*\n(.*?)^\s*\.end_amdhsa_kernel", s, re.S | re.M):
-        for k in ("sgd_kernel", "sgd_groups_kernel", "grad_sqnorm_kernel", "clip_coef_kernel", "grad_accumulate_kernel"):
+        for k in (plain, groups, "grad_sqnorm_kernel", "clip_coef_kernel", "grad_accumulate_kernel"):
             if re.search(r"\d" + k + "E", m.group(1)):
                 bodies[k] = m.group(2)
     assert len(bodies) == 5, sorted(bodies)
     ops = lambda k, pat: len(re.findall(r"^\s*" + pat + r"\b", bodies[k], re.M))
     for k, b in bodies.items():
         assert ".amdhsa_private_segment_fixed_size 0" in b and "scratch_" not in b, k
-    for k in ("sgd_groups_kernel", "grad_sqnorm_kernel", "grad_accumulate_kernel"):
+    for k in (plain, groups, "grad_sqnorm_kernel", "grad_accumulate_kernel"):
         assert ops(k, "global_load_dwordx4") >= 1 and ops(k, "global_load_dword") == 0, k
-    assert ops("sgd_groups_kernel", "global_store_dwordx4") == 2 and ops("grad_accumulate_kernel", "global_store_dwordx4") >= 1
+    for k in (plain, groups):
+        assert ops(k, "global_store_dwordx4") == 2, k
+        assert ops(k, "v_pk_fma_f32") == 6 and ops(k, "v_pk_mul_f32") == 2, k
+    assert ops("grad_accumulate_kernel", "global_store_dwordx4") >= 1
     for pat in ("v_pk_mul_f32", "v_pk_fma_f32", "v_fma_f32", "v_add_f32", "v_pk_add_f32"):
-        assert ops("sgd_groups_kernel", pat) == ops("sgd_kernel", pat), pat
-    assert ops("sgd_kernel", "v_pk_fma_f32") == 6 and ops("sgd_kernel", "v_pk_mul_f32") == 2
-    assert ops("sgd_groups_kernel", "s_load_dwordx2") >= 1          # the per-tile binary search
+        assert ops(groups, pat) == ops(plain, pat), pat
+    assert ops(groups, "s_load_dwordx2") >= 1          # the per-tile binary search
+    # ... which <false> does not have: none of <true>'s 8-byte scalar loads of table entries, and no lane walk over them either
+    assert ops(plain, "s_load_dwordx2") <= ops(groups, "s_load_dwordx2") - 1
+    assert ops(plain, "global_load_dwordx2") == 0 and ops(plain, "global_load_dwordx4") == 3
     for k in ("grad_sqnorm_kernel", "clip_coef_kernel"):
         assert "atomic" not in bodies[k] and ops(k, "v_fma_f64") + ops(k, "v_add_f64") + ops(k, "v_mul_f64") >= 1, k
