@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("ERD_HIP_LIB") or os.path.join(_HERE, "lib", "liberd_h
 
 ERD_MAX_SEG = 5
 ERD_MAX_TAPS = 9
+ERD_MAX_GROUPS = 8
 ERD_SQNORM_PARTS = 1024
 
 c_float_p = C.c_void_p  # raw device pointers travel as integers
@@ -51,7 +52,13 @@ class WgradDesc(C.Structure):
                 ("dy", i32 * ERD_MAX_TAPS), ("dx", i32 * ERD_MAX_TAPS),
                 ("in_stride", i32), ("out_stride", i32), ("oy", i32), ("ox", i32),
                 ("part", C.c_void_p), ("nsplit", i32), ("bf16_multiplicands", i32),
-                ("x_bf16", i32), ("dz_bf16", i32), ("limbs3", i32)]
+                ("x_bf16", i32), ("dz_bf16", i32), ("limbs3", i32),
+                ("ngroups", i32), ("gx", C.c_void_p * ERD_MAX_GROUPS), ("gdz", C.c_void_p * ERD_MAX_GROUPS)]
+
+
+class WgradReduceGroups(C.Structure):
+    _fields_ = [("ngroups", i32), ("w", C.c_void_p * ERD_MAX_GROUPS), ("rowscale", C.c_void_p * ERD_MAX_GROUPS),
+                ("dW", C.c_void_p * ERD_MAX_GROUPS), ("rowdot", C.c_void_p * ERD_MAX_GROUPS)]
 
 
 class BnFoldItem(C.Structure):
@@ -98,6 +105,7 @@ _SIGNATURES = {
     "erd_wgrad_row3_slices": [C.POINTER(WgradDesc)],
     "erd_wgrad_reduce": [P, i32, i32, i32, P, P, P, i32, P, P],
     "erd_wgrad_reduce_rows": [P, i32, i32, i32, i32, P, i32, P],
+    "erd_wgrad_reduce_grouped": [P, i32, i32, i32, C.POINTER(WgradReduceGroups), i32, P],
     "erd_weight_transpose": [P, P, P, i32, i32, i32, i32, P],
     "erd_weight_transpose_bf16": [P, P, P, i32, i32, i32, i32, P],
     "erd_stem_conv7x7_bn_relu": [P, P, P, P, P, i32, i32, i32, P],

@@ -1435,8 +1435,11 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
     const int ky = bx / nci;                                   // ROW3: kernel row; otherwise the tap index
     const int ci0 = (bx % nci) * BNR;
     const int co0 = by * BMR;
+    // grouped launch (erd_wgrad_desc::ngroups > 1): split bz is local split bz % nsplit of group bz / nsplit -- the K range, the tables
+    // and the walker are those of a launch of that group alone, only the two base pointers (below) and the slab index bz differ
+    const int grp = p.ngroups > 1 ? bz / p.nsplit : 0;
     const int per = (nslices + p.nsplit - 1) / p.nsplit;
-    const int kt_begin = bz * per;
+    const int kt_begin = (bz - grp * p.nsplit) * per;
     const int kt_end = min(nslices, kt_begin + per);
 
     const int wave = tid >> 6, lane = tid & 63;
@@ -1545,8 +1548,16 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
         }
     };
 
-    const __amdgpu_buffer_rsrc_t rs_dz = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dz), 0, (int)(p.dz_elems * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)(p.x_elems * 4), 0x00020000);
+    // (a chain of scalar selects: indexing the by-value descriptor with grp would move the whole descriptor to scratch)
+    const float* base_dz = p.dz;
+    const float* base_x = p.x;
+    if (p.ngroups > 1) {
+#pragma unroll
+        for (int g = 0; g < ERD_MAX_GROUPS; ++g)
+            if (g == grp) { base_dz = p.gdz[g]; base_x = p.gx[g]; }
+    }
+    const __amdgpu_buffer_rsrc_t rs_dz = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base_dz), 0, (int)(p.dz_elems * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base_x), 0, (int)(p.x_elems * 4), 0x00020000);
 
     // ---- staging roles: threads [0, NA) own a dz micro-tile (4 px x 4 co), threads [128, 128 + 80) an x micro-tile (4 entries x 4 ci)
     constexpr int NA = (BMR / 4) * 4;                           // dz micro-tiles: (BMR / 4) channel groups x 4 pixel groups
@@ -1982,14 +1993,22 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_bf16_kernel(const erd_
 // dW[co][k] (+)= rowscale[co] * sum_s part[s][co][k];  rowdot[co] += sum_k w[co][k] * G[co][k]
 // grid (Cout, K/1024): every thread sums one float4 column of the nsplit slabs (coalesced across the block);
 // rowdot is accumulated with one atomic per block (the caller zeroes it).
+// groups (erd_wgrad_reduce_grouped): group g = blockIdx.z sums slabs [g * nsplit, (g + 1) * nsplit) with its own w / rowscale / dW / rowdot
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, int nsplit, int Cout,
                                                             int K, const float* __restrict__ w,
                                                             const float* __restrict__ rowscale,
                                                             float* __restrict__ dW, int accumulate,
-                                                            float* __restrict__ rowdot) {
+                                                            float* __restrict__ rowdot, const erd_wgrad_reduce_groups groups) {
     const int co = blockIdx.x;
     const int k = (blockIdx.y * 256 + threadIdx.x) * 4;
     const int64_t slab = (int64_t)Cout * K;
+    if (groups.ngroups > 0) {
+        const int g = blockIdx.z;
+        part += (int64_t)g * nsplit * slab;
+#pragma unroll
+        for (int i = 0; i < ERD_MAX_GROUPS; ++i)      // (scalar selects: a dynamic index would move the table to scratch)
+            if (i == g) { w = groups.w[i]; rowscale = groups.rowscale[i]; dW = groups.dW[i]; rowdot = groups.rowdot[i]; }
+    }
     const float rs = rowscale ? rowscale[co] : 1.f;
     float dot = 0.f;
     if (k < K) {
@@ -2338,10 +2357,17 @@ extern "C" int erd_wgrad_row3_slices(const erd_wgrad_desc* d) {
 }
 
 extern "C" int erd_conv_wgrad(const erd_wgrad_desc* d, erd_stream_t stream) {
-    ERD_REQUIRE(d != nullptr && d->x && d->dz && d->part, "wgrad: null pointer");
+    ERD_REQUIRE(d != nullptr && d->part, "wgrad: null pointer");
+    ERD_REQUIRE(d->ngroups >= 1 && d->ngroups <= ERD_MAX_GROUPS, "wgrad: ngroups=%d", d->ngroups);
+    if (d->ngroups > 1) {      // a grouped launch: the three-limb kernels only, every group's two base pointers given
+        ERD_REQUIRE(d->limbs3 && !d->bf16_multiplicands && !d->x_bf16 && !d->dz_bf16 && d->Cin % 4 == 0,
+                    "wgrad: ngroups=%d needs the three-limb form (limbs3, fp32 maps)", d->ngroups);
+        for (int g = 0; g < d->ngroups; ++g) ERD_REQUIRE(d->gx[g] && d->gdz[g], "wgrad: null pointer in group %d", g);
+    } else
+        ERD_REQUIRE(d->x && d->dz, "wgrad: null pointer");
     ERD_REQUIRE(d->ntaps >= 1 && d->ntaps <= ERD_MAX_TAPS, "wgrad: ntaps=%d", d->ntaps);
     ERD_REQUIRE(d->Cin % 4 == 0 && d->Cout % 4 == 0, "wgrad: Cin=%d Cout=%d must be multiples of 4", d->Cin, d->Cout);
-    ERD_REQUIRE(d->nsplit >= 1 && d->nsplit <= 65535, "wgrad: nsplit=%d", d->nsplit);
+    ERD_REQUIRE(d->nsplit >= 1 && d->nsplit * d->ngroups <= 65535, "wgrad: nsplit=%d", d->nsplit);
     ERD_REQUIRE(d->nseg >= 1 && d->nseg <= ERD_MAX_SEG, "wgrad: nseg=%d", d->nseg);
     int64_t npix = 0;
     for (int l = 0; l < d->nseg; ++l) npix += (int64_t)d->seg[l].N * d->seg[l].GH * d->seg[l].GW;
@@ -2388,7 +2414,7 @@ extern "C" int erd_conv_wgrad(const erd_wgrad_desc* d, erd_stream_t stream) {
             attr_done3[fm - 1] = true;
         }
         static const int row3_xcd = getenv("ERD_WGRAD_XCD") ? atoi(getenv("ERD_WGRAD_XCD")) : 1;
-        hipLaunchKernelGGL(kern, dim3(nci * 3 * nco * d->nsplit), dim3(NTHREADS), lds, (hipStream_t)stream, *d,
+        hipLaunchKernelGGL(kern, dim3(nci * 3 * nco * d->nsplit * d->ngroups), dim3(NTHREADS), lds, (hipStream_t)stream, *d,
                            nslices | (row3_xcd ? (1 << 30) : 0));
         return erd::check_launch("conv_wgrad_row3_x3");
     }
@@ -2406,7 +2432,7 @@ extern "C" int erd_conv_wgrad(const erd_wgrad_desc* d, erd_stream_t stream) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             attr_done1 = true;
         }
-        hipLaunchKernelGGL(kern, dim3(nci * d->ntaps * nco * d->nsplit), dim3(NTHREADS), lds, (hipStream_t)stream, *d,
+        hipLaunchKernelGGL(kern, dim3(nci * d->ntaps * nco * d->nsplit * d->ngroups), dim3(NTHREADS), lds, (hipStream_t)stream, *d,
                            nslices | (xcd_order_enabled() ? (1 << 30) : 0));
         return erd::check_launch("conv_wgrad_x3");
     }
@@ -2441,8 +2467,24 @@ extern "C" int erd_wgrad_reduce(const float* part, int nsplit, int Cout, int K, 
     // accumulate: bit 0 = add into dW, bit 1 = rowdot is already zero (comes from the caller's zero arena: no memset)
     if (rowdot && !(accumulate & 2)) (void)hipMemsetAsync(rowdot, 0, sizeof(float) * Cout, (hipStream_t)stream);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(Cout, (K + 1023) / 1024), dim3(256), 0, (hipStream_t)stream, part,
-                       nsplit, Cout, K, w, rowscale, dW, accumulate & 1, rowdot);
+                       nsplit, Cout, K, w, rowscale, dW, accumulate & 1, rowdot, erd_wgrad_reduce_groups{});
     return erd::check_launch("wgrad_reduce");
+}
+
+extern "C" int erd_wgrad_reduce_grouped(const float* part, int nsplit, int Cout, int K, const erd_wgrad_reduce_groups* groups,
+                                        int accumulate, erd_stream_t stream) {
+    ERD_REQUIRE(part && groups && nsplit >= 1 && Cout >= 1 && K >= 4 && K % 4 == 0, "wgrad_reduce_grouped: bad args");
+    ERD_REQUIRE(groups->ngroups >= 1 && groups->ngroups <= ERD_MAX_GROUPS, "wgrad_reduce_grouped: ngroups=%d", groups->ngroups);
+    for (int g = 0; g < groups->ngroups; ++g) {
+        ERD_REQUIRE(groups->dW[g], "wgrad_reduce_grouped: group %d has no dW", g);
+        ERD_REQUIRE(!groups->rowdot[g] || groups->w[g], "wgrad_reduce_grouped: rowdot of group %d needs w", g);
+    }
+    if (!(accumulate & 2))
+        for (int g = 0; g < groups->ngroups; ++g)
+            if (groups->rowdot[g]) (void)hipMemsetAsync(groups->rowdot[g], 0, sizeof(float) * Cout, (hipStream_t)stream);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(Cout, (K + 1023) / 1024, groups->ngroups), dim3(256), 0, (hipStream_t)stream, part,
+                       nsplit, Cout, K, nullptr, nullptr, nullptr, accumulate & 1, nullptr, *groups);
+    return erd::check_launch("wgrad_reduce_grouped");
 }
 
 extern "C" int erd_wgrad_reduce_rows(const float* part, int nsplit, int Cout_slab, int Cout, int K, float* dW,
@@ -2450,7 +2492,7 @@ extern "C" int erd_wgrad_reduce_rows(const float* part, int nsplit, int Cout_sla
     ERD_REQUIRE(part && dW && nsplit >= 1 && K % 4 == 0 && Cout >= 1 && Cout <= Cout_slab, "wgrad_reduce_rows: bad args");
     // the kernel's block co reduces row co of each [Cout_slab][K] slab: a grid of Cout blocks leaves the padding rows out
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(Cout, (K + 1023) / 1024), dim3(256), 0, (hipStream_t)stream, part,
-                       nsplit, Cout_slab, K, nullptr, nullptr, dW, accumulate & 1, nullptr);
+                       nsplit, Cout_slab, K, nullptr, nullptr, dW, accumulate & 1, nullptr, erd_wgrad_reduce_groups{});
     return erd::check_launch("wgrad_reduce_rows");
 }
 

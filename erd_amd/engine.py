@@ -160,18 +160,19 @@ class BucketedGradSync:
         self.late_buckets = 0            # buckets that were not complete when backward ended (diagnostic)
         self.missing: List[str] = []     # ... and the parameters that had not reported a gradient by then (last occurrence)
         self._seen: List[bool] = []
+        self._sunk: List[bool] = []      # ... by a sink's report, and autograd's call for the same parameter has not come yet
         self.repeats = set()             # parameters that reported more than once in a step (diagnostic: the contract is once)
         self._warned_late = False
         self._next = 0
         self.issued_in_backward = 0      # buckets released by a hook (not by wait()) in the last step (diagnostic)
         for i, p in enumerate(flat.params):
-            hook = self._make_hook(i)
-            p.register_post_accumulate_grad_hook(hook)
-            p._erd_sink_notify = hook      # gradients written straight into the flat slot bypass AccumulateGrad
+            p.register_post_accumulate_grad_hook(self._make_hook(i, False))
+            p._erd_sink_notify = self._make_hook(i, True)      # gradients written straight into the flat slot bypass AccumulateGrad
 
     def arm(self) -> None:
         self._remaining = [len(m) for (_, _, m) in self.flat.buckets]
         self._seen = [False] * len(self.flat.params)
+        self._sunk = [False] * len(self.flat.params)
         self._works = []
         self._next = 0                   # collectives are issued strictly in bucket order: the same order on every rank
         self.issued_in_backward = 0
@@ -221,14 +222,20 @@ class BucketedGradSync:
         elif w is not None:
             self._works.append(w)
 
-    def _make_hook(self, i: int):
+    def _make_hook(self, i: int, sink: bool):
+        """sink: the report of a backward kernel that wrote the flat slot itself (functional._sunk); otherwise autograd's
+        post-accumulate hook -- which autograd also runs once for the None such a node hands back for that parameter, after the
+        node: that call follows the sink's report and is not a second report"""
         def hook(_p):
             if not self._remaining:
                 return
             if self._seen[i]:            # (one notification per parameter and step: a second one must not drive the countdown
-                self.repeats.add(self.flat.names[i])      # below zero -- the in-order issue loop waits for exactly zero)
+                if sink or not self._sunk[i]:                 # below zero -- the in-order issue loop waits for exactly zero)
+                    self.repeats.add(self.flat.names[i])
+                self._sunk[i] = False
                 return
             self._seen[i] = True
+            self._sunk[i] = sink
             b = self.flat.bucket_of[i]
             self._remaining[b] -= 1
             # issue every complete bucket at the head of the queue.  A bucket that completes before an earlier one (a

@@ -35,6 +35,7 @@ def _to_oihw(dw_ohwi: Tensor) -> Tensor:
 # enqueued on an auxiliary HIP stream; two MFMA-bound kernels in flight fill each other's ragged dispatch rounds.
 # ---------------------------------------------------------------------------------------------------
 _AUX = {}
+import contextlib as _contextlib
 import os as _os
 WGRAD_ON_AUX_STREAM = _os.environ.get('ERD_WGRAD_AUX', '0') != '0'
 TOWERS_ON_TWO_STREAMS = _os.environ.get('ERD_TOWER_AUX', '1') != '0'
@@ -63,6 +64,13 @@ def _may_fork(cur) -> bool:
 # Only with gradient sinks (ERDTrainer, which owns the join): the results land in the flat gradient buffer, nothing is
 # handed back to autograd from the auxiliary stream.
 WGRAD_TRAIL = _os.environ.get('ERD_WGRAD_TRAIL', '1') != '0'
+# Grouped weight gradients (ResLayerFn.backward, f32x3 with the three-limb forms on): the identity blocks of a stage run the same three
+# convolution shapes, and every weight gradient is split along K until one launch fills the chip on its own.  The same-shape
+# gradients of a stage are collected and go out as ONE launch each (K.conv_wgrad_partials_grouped, up to WGRAD_GROUP_CAP members):
+# G times longer K loops per workgroup, G times fewer partial-slab bytes and reduce launches (_WgradGroups).  0: every block
+# launches its own as it goes (A/B aid).
+WGRAD_GROUPED = _os.environ.get('ERD_WGRAD_GROUPED', '1') != '0'
+WGRAD_GROUP_CAP = 8      # members per launch (erd_hip.h ERD_MAX_GROUPS); also bounds the gradient maps kept alive (R101's layer3: 22 identity blocks)
 RES_LAYER_NODE = _os.environ.get('ERD_RES_LAYER', '1') != '0'    # a whole ResNet stage as one autograd node (ResLayerFn): A/B aid
 HEAD_TRAIL = _os.environ.get('ERD_HEAD_TRAIL', '0') != '0'      # the head towers' weight gradients too (A/B aid: see _wgrad_plain)
 _TRAIL = {}
@@ -178,6 +186,67 @@ def _emit_wgrad(w: Tensor, part: Tensor, S: int, wk: Tensor, scale: Optional[Ten
     dWk = torch.empty_like(wk)
     K.wgrad_reduce(part, S, wk, scale, dWk, False, rowdot, rowdot_zeroed=True)
     return _to_oihw(dWk)
+
+
+class _WgradGroups:
+    """The weight gradients of one stage's backward pass, collected by shape.  add() takes a weight gradient of _bottleneck_backward's
+    wgrad() whose needed gradients all have a flat slot (the ones that trail under WGRAD_TRAIL); a key -- (k, stride, pad, geometry of x and dz) -- is
+    launched when it holds WGRAD_GROUP_CAP members, and flush() launches what is left at the end of the stage.  One launch is one
+    _Trail entry (the current stream without WGRAD_TRAIL): the grouped partial slabs, the grouped reduce, then every member's d gamma / d beta folds as in the ungrouped
+    path.  A key with one member goes through the ungrouped path.  A parameter reports (_sunk) only after the launches that
+    produce its gradient are queued, and by then every other launch of its block is queued too (BucketedGradSync's contract)."""
+
+    def __init__(self, device, eps: float):
+        self.dev, self.eps, self.keys = device, eps, {}
+        self.launches = []           # members per launch (diagnostic; the tests read it)
+
+    @staticmethod
+    def takes(xin: Tensor, dz: Tensor) -> bool:
+        # (not while a whole-step graph is warmed up or captured: the captured step keeps one launch per block -- with grouped
+        #  launches in the capture the replayed step left the eager one after the first update, EXPERIMENTS 7n)
+        return WGRAD_GROUPED and CAPTURE_ORIGIN is None and K.COMPUTE == "f32x3" and K.WGRAD_X3 and K.WGRAD_X3_GENERIC and xin.dtype == torch.float32 \
+            and dz.dtype == torch.float32 and _os.environ.get("ERD_WGRAD_ROW3", "1") != "0"
+
+    def add(self, single, xin, dz, k, s, pad, scale, dbeta, prm, need3) -> None:
+        key = (k, s, pad, xin.shape, xin.stride(), dz.shape, dz.stride())
+        q = self.keys.setdefault(key, [])
+        q.append((single, xin, dz, k, s, pad, scale, dbeta, prm, need3))
+        if len(q) == WGRAD_GROUP_CAP:
+            self._launch(self.keys.pop(key))
+
+    def flush(self) -> None:
+        for key in list(self.keys):
+            self._launch(self.keys.pop(key))
+
+    def _launch(self, q) -> None:
+        self.launches.append(len(q))
+        if len(q) == 1:
+            q[0][0]()
+            return
+        _, _, _, k, s, pad = q[0][:6]
+        with (_Trail(self.dev, *[t for m in q for t in (m[1], m[2], m[6], m[7])]) if WGRAD_TRAIL else _contextlib.nullcontext()):
+            part, S = K.conv_wgrad_partials_grouped([[m[1]] for m in q], [[m[2]] for m in q], k, s, pad)
+            wks = [ohwi(m[8][0]) for m in q]
+            rowdots = [K.zeros_f32(m[6].numel(), m[6].device) if m[9][1] else None for m in q]
+            K.wgrad_reduce_grouped(part, S, wks, [m[6] for m in q], [ohwi(_sink(m[8][0])) for m in q], True, rowdots, rowdot_zeroed=True)
+            for m, rowdot in zip(q, rowdots):
+                (w, g, b, mean, var), (_, need_g, need_b), dbeta = m[8], m[9], m[7]
+                _sunk(w)
+                if need_g:
+                    rep = dbeta.dim() == 2
+                    bs_fold = (_sink(b) if need_b else None) if rep else None
+                    fold = None if not rep else (bs_fold if bs_fold is not None else torch.empty_like(dbeta[0]))
+                    K.bn_dgamma(rowdot, dbeta, mean, var, self.eps, out=_sink(g), dbeta_out=fold)
+                    _sunk(g)
+                    if rep:
+                        dbeta = fold
+                elif dbeta.dim() == 2:
+                    dbeta = dbeta.sum(0)
+                if need_b:
+                    bs = _sink(b)
+                    if dbeta.data_ptr() != bs.data_ptr():   # (the projection shortcut shares conv3's column sums)
+                        bs.add_(dbeta)
+                    _sunk(b)
 
 
 def _bn_fold_cached(gamma, beta, mean, var, eps):
@@ -403,18 +472,19 @@ class BottleneckFn(Function):
         return (dx, None, None, *grads)
 
 
-def _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_p, need_x, stride, eps, dz3, db3, out_mask=None):
+def _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_p, need_x, stride, eps, dz3, db3, out_mask=None, groups=None):
     """Backward of one bottleneck given dz3 = dy * (y > 0) and its column sums db3 (a [C] vector that may BE d beta's flat slot,
     or a replicated [copies, C] accumulator of a gradient convolution's epilogue).  need_p: needs-gradient flags of the block's
     parameters, 5 per convolution (w, gamma, beta, mean, var).  Returns (dx, grads).  With `out_mask` (the block's own input x,
     which is the previous block's post-ReLU output) the last input-gradient launch ALSO applies that ReLU's mask and column-sums
     the result into a fresh replicated accumulator: it then returns ((dz3 of the previous block, its db3), grads) -- the
-    stand-alone ReLU-backward pass between two blocks of a stage disappears (identity-shortcut blocks only)."""
+    stand-alone ReLU-backward pass between two blocks of a stage disappears (identity-shortcut blocks only).  With `groups` (a
+    _WgradGroups of the stage) the weight gradients that would trail are handed to it instead of being launched here."""
     has_down = sd is not None
     dev = x.device
     grads = [None] * (5 * len(P))
 
-    def wgrad(idx, xin, dz, k, s, pad, scale, dbeta):
+    def wgrad(idx, xin, dz, k, s, pad, scale, dbeta, collect=True):
         """dW (scaled by the folded BN), d gamma, d beta of conv `idx`"""
         w, g, b, m, v = P[idx]
         base = 5 * idx
@@ -422,7 +492,12 @@ def _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_p, need_x, stride, e
             return
         wk = ohwi(w)
         trail = None
-        if WGRAD_TRAIL and all((not need_p[base + q]) or _sink(t) is not None for q, t in enumerate((w, g, b))):
+        sunk = all((not need_p[base + q]) or _sink(t) is not None for q, t in enumerate((w, g, b)))
+        if collect and groups is not None and sunk and need_p[base] and groups.takes(xin, dz):
+            groups.add(lambda: wgrad(idx, xin, dz, k, s, pad, scale, dbeta, collect=False), xin, dz, k, s, pad, scale, dbeta, (w, g, b, m, v),
+                       tuple(need_p[base:base + 3]))
+            return
+        if WGRAD_TRAIL and sunk:
             trail = _Trail(dev, xin, dz, scale, dbeta)
             trail.__enter__()
         try:
@@ -551,6 +626,7 @@ class ResLayerFn(Function):
         nb = len(blocks)
         dz3 = db3 = None
         dx = None
+        groups = _WgradGroups(dy.device, ctx.eps) if WGRAD_GROUPED else None
         for i in range(nb - 1, -1, -1):
             stride, has_down, a0 = ctx.meta[i]
             x, o1, o2, y, s1, s2, s3 = acts[a0:a0 + 7]
@@ -566,7 +642,7 @@ class ResLayerFn(Function):
             fuse = i > 0 and not has_down
             need_x = need[0] if i == 0 else True
             out, g = _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_b[i], need_x, stride, ctx.eps, dz3, db3,
-                                          out_mask=x if fuse else None)
+                                          out_mask=x if fuse else None, groups=groups)
             base = sum(ctx.counts[:i])
             grads_all[base:base + len(g)] = g
             if i == 0:
@@ -579,6 +655,9 @@ class ResLayerFn(Function):
                 s_ = _sink(pb3) if need_b[i - 1][5 * 2 + 2] else None
                 dz3, db3 = K.relu_bwd_colsum(prev_y, out, True,
                                              colsum_into=s_ if s_ is not None else K.zeros_f32(prev_y.shape[3], x.device))
+        if groups is not None:
+            groups.flush()
+            ResLayerFn.last_group_launches = groups.launches
         return (dx, None, None, None, *grads_all)
 
 

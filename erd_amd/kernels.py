@@ -975,8 +975,10 @@ def conv_wgrad_partials(xs: Sequence[Tensor], dzs: Sequence[Tensor], k: int, str
     return part, S
 
 
-def _wgrad_desc(xs, dzs, k, stride, pad, xoff, zoff):
-    """the launch descriptor of a weight gradient (base pointers and the partial-slab pointer left to the caller)"""
+def _wgrad_desc(xs, dzs, k, stride, pad, xoff, zoff, ngroups: int = 1):
+    """the launch descriptor of a weight gradient (base pointers and the partial-slab pointer left to the caller).
+    ngroups > 1: xs / dzs are the maps of ONE of `ngroups` independent weight gradients of this geometry that share the launch
+    (erd_wgrad_desc::ngroups): the split count is the per-group one, sized so that all groups together fill the one dispatch round."""
     Cin, Cout = xs[0].shape[3], dzs[0].shape[3]
     npix = sum(dz.shape[0] * dz.shape[1] * dz.shape[2] for dz in dzs)
     d = WgradDesc()
@@ -1007,7 +1009,7 @@ def _wgrad_desc(xs, dzs, k, stride, pad, xoff, zoff):
         bmr = 128 if Cout > 64 else 64
         groups = ((Cout + bmr - 1) // bmr) * ((Cin + 63) // 64) * 3
         target = _one_round(int(_os.environ.get("ERD_WGRAD_ROW3_X3_TARGET", "768")))      # three workgroups per CU: one dispatch round
-        S = int(max(1, min(target // groups, row3 // 16 if row3 >= 16 else 1, 512)))
+        S = int(max(1, min(target // (groups * ngroups), row3 // 16 if row3 >= 16 else 1, 512)))
     elif row3:      # three taps per workgroup, two workgroups per CU: ONE whole dispatch round of (cout, cin, ky, split) workgroups
         # (measured best: 2 or 3 rounds pay more partial-slab traffic than they gain; a ragged extra round costs 15-40 %)
         bme = 64 if Cout <= 64 else (96 if Cout <= 96 else 128)        # rows of the kernel's output tile (erd_conv_wgrad)
@@ -1017,13 +1019,74 @@ def _wgrad_desc(xs, dzs, k, stride, pad, xoff, zoff):
     elif d.limbs3:      # three-limb form of the other layers: 128 x 128 channels, one tap per workgroup, one dispatch round of three per CU
         tiles = ((Cout + 127) // 128) * ((Cin + 127) // 128) * k * k
         kt = (npix + 15) // 16
-        S = int(max(1, min(_one_round(int(_os.environ.get("ERD_WGRAD_X3_TARGET", "768"))) // tiles, kt // 8 if kt >= 8 else 1, 512)))
+        S = int(max(1, min(_one_round(int(_os.environ.get("ERD_WGRAD_X3_TARGET", "768"))) // (tiles * ngroups), kt // 8 if kt >= 8 else 1, 512)))
     else:
         S = _pick_nsplit(npix, Cout, Cin, k * k)
     d.nsplit = S
-    flop = 2.0 * npix * Cout * Cin * k * k
-    nbytes = 4.0 * (sum(t.numel() for t in xs) + sum(t.numel() for t in dzs) + S * Cout * k * k * Cin)
-    return d, S, flop, nbytes, f"px{npix} {Cin}->{Cout} k{k}s{stride} S{S}", Cout, Cin, bool(row3)
+    d.ngroups = ngroups
+    flop = 2.0 * npix * Cout * Cin * k * k * ngroups
+    nbytes = 4.0 * ngroups * (sum(t.numel() for t in xs) + sum(t.numel() for t in dzs) + S * Cout * k * k * Cin)
+    tag = f"px{npix} {Cin}->{Cout} k{k}s{stride} S{S}" + (f" G{ngroups}" if ngroups > 1 else "")
+    return d, S, flop, nbytes, tag, Cout, Cin, bool(row3)
+
+
+def conv_wgrad_partials_grouped(xs_per_group: Sequence[Sequence[Tensor]], dzs_per_group: Sequence[Sequence[Tensor]], k: int, stride: int,
+                                pad: int, nsplit: Optional[int] = None):
+    """G independent weight gradients of ONE geometry (the same convolution of a ResNet stage's identity blocks) in one launch of the
+    three-limb kernels: returns (part [G * S, Cout, k*k, Cin], S) -- slabs [g * S, (g + 1) * S) are group g's, each what a launch of
+    that group alone at split count S writes.  S: the one-round formula of conv_wgrad_partials with G times the tiles (every
+    workgroup's K loop is G times longer than in G launches of their own, the slab bytes G times fewer), or `nsplit`."""
+    G = len(xs_per_group)
+    assert 1 <= G <= _lib.ERD_MAX_GROUPS and len(dzs_per_group) == G, f"1 .. {_lib.ERD_MAX_GROUPS} groups"
+    xs0, dzs0 = xs_per_group[0], dzs_per_group[0]
+    _require_gpu(*[t for xs in xs_per_group for t in xs], *[t for dzs in dzs_per_group for t in dzs])
+    xbs = [min(x.data_ptr() for x in xs) for xs in xs_per_group]
+    zbs = [min(z.data_ptr() for z in dzs) for dzs in dzs_per_group]
+    offs = lambda ts, b: tuple((t.data_ptr() - b) // t.element_size() for t in ts)
+    xoff, zoff = offs(xs0, xbs[0]), offs(dzs0, zbs[0])
+    for g in range(1, G):
+        assert (_geom(xs_per_group[g]), _geom(dzs_per_group[g]), offs(xs_per_group[g], xbs[g]), offs(dzs_per_group[g], zbs[g])) == \
+            (_geom(xs0), _geom(dzs0), xoff, zoff), "the groups of a grouped weight gradient share one geometry"
+    cache = _desc_cache()
+    key = ("wgrad_grouped", G, k, stride, pad, _geom(xs0), _geom(dzs0), xoff, zoff, COMPUTE, _os.environ.get("ERD_WGRAD_ROW3", "1"), WGRAD_X3,
+           WGRAD_X3_GENERIC, CU_RESERVE)
+    ent = cache.get(key)
+    if ent is None:
+        ent = cache[key] = _wgrad_desc(xs0, dzs0, k, stride, pad, xoff, zoff, ngroups=G)
+    d, S, flop, nbytes, tag, Cout, Cin, row3 = ent
+    if not d.limbs3:
+        raise RuntimeError("conv_wgrad_partials_grouped: only the three-limb weight-gradient kernels (compute mode f32x3) take groups")
+    slab = Cout * k * k * Cin
+    if nsplit is not None:
+        nbytes += 4.0 * G * (int(nsplit) - S) * slab
+        S = int(nsplit)
+    d.nsplit = S
+    d.x, d.dz = xbs[0], zbs[0]
+    for g in range(G):
+        d.gx[g], d.gdz[g] = xbs[g], zbs[g]
+    part = ws_float("wgrad_part", G * S * slab, xs0[0].device)
+    d.part = part.data_ptr()
+    _timed_call("conv_wgrad_row3" if row3 else "conv_wgrad", flop, "erd_conv_wgrad", C.byref(d), _stream(), nbytes=nbytes if _TIMING is not None else 0.0,
+                tag=tag if TIMING_DETAIL else "")
+    return part, S
+
+
+def wgrad_reduce_grouped(part: Tensor, S: int, ws: Sequence[Tensor], rowscales: Sequence[Optional[Tensor]], dWs: Sequence[Tensor],
+                         accumulate: bool, rowdots: Sequence[Optional[Tensor]], rowdot_zeroed: bool = False) -> None:
+    """wgrad_reduce for the slabs of conv_wgrad_partials_grouped, one launch: group g reduces slabs [g * S, (g + 1) * S) into dWs[g]"""
+    G = len(ws)
+    assert 1 <= G <= _lib.ERD_MAX_GROUPS and len(rowscales) == len(dWs) == len(rowdots) == G
+    Cout = ws[0].shape[0]
+    Kd = ws[0].numel() // Cout
+    t = _lib.WgradReduceGroups()
+    t.ngroups = G
+    for g in range(G):
+        assert ws[g].shape == ws[0].shape and dWs[g].numel() == ws[0].numel()
+        t.w[g] = ws[g].data_ptr()
+        t.rowscale[g] = 0 if rowscales[g] is None else rowscales[g].data_ptr()
+        t.dW[g] = dWs[g].data_ptr()
+        t.rowdot[g] = 0 if rowdots[g] is None else rowdots[g].data_ptr()
+    call("erd_wgrad_reduce_grouped", _p(part), S, Cout, Kd, C.byref(t), (1 if accumulate else 0) | (2 if rowdot_zeroed else 0), _stream())
 
 
 def wgrad_reduce_rows(part: Tensor, S: int, Cout_slab: int, dW: Tensor, accumulate: bool) -> None:

@@ -30,6 +30,7 @@ extern "C" {
 #define ERD_ABI_VERSION 6
 #define ERD_MAX_SEG 5   /* FPN levels batched in one launch */
 #define ERD_MAX_TAPS 9
+#define ERD_MAX_GROUPS 8 /* same-shape weight gradients batched in one launch (erd_wgrad_desc::ngroups) */
 
 #define ERD_EINVAL (-1)
 #define ERD_EUNSUPPORTED (-2)
@@ -217,6 +218,13 @@ typedef struct {
                              * split in the kernel's transposing loader (4 pixels x 4 channels per thread).  3x3 / stride-1 layers:
                              * three taps of a kernel row per workgroup (the taps are register shifts of the packed pixel vectors);
                              * every other layer: one tap, 128 x 128 channels per workgroup.  Cin % 4 == 0. */
+    int ngroups;            /* 1: one weight gradient (x / dz above).  2 .. ERD_MAX_GROUPS, three-limb forms only: that many
+                             * INDEPENDENT weight gradients of one geometry (a ResNet stage's identity blocks) in one launch of
+                             * ngroups * nsplit splits.  The segment list, Cin, Cout, taps and extents describe ONE group; group g
+                             * reads gx[g] / gdz[g] (any addresses, any order; x / dz are not read) and writes slabs
+                             * part[g * nsplit .. (g + 1) * nsplit), each exactly what a launch of its own with this nsplit writes. */
+    const float* gx[ERD_MAX_GROUPS];
+    const float* gdz[ERD_MAX_GROUPS];
 } erd_wgrad_desc;
 int erd_conv_wgrad(const erd_wgrad_desc* d, erd_stream_t stream);
 /* > 0: the layer takes the three-taps-per-workgroup kernel (3x3, stride 1, pad 1, fp32) and this is its number of
@@ -235,6 +243,18 @@ int erd_wgrad_reduce(const float* part, int nsplit, int Cout, int K, const float
  * of 4, gfl_head.py:224-229).  accumulate: bit 0 = add into dW. */
 int erd_wgrad_reduce_rows(const float* part, int nsplit, int Cout_slab, int Cout, int K, float* dW, int accumulate,
                           erd_stream_t stream);
+/* erd_wgrad_reduce for the slabs of a grouped launch (erd_wgrad_desc::ngroups), one launch: group g sums slabs
+ * [g * nsplit, (g + 1) * nsplit) in erd_wgrad_reduce's order into its own dW, with its own w / rowscale / rowdot
+ * (rowscale and rowdot may be null per group; a rowdot needs the group's w).  accumulate as in erd_wgrad_reduce. */
+typedef struct {
+    int ngroups;
+    const float* w[ERD_MAX_GROUPS];
+    const float* rowscale[ERD_MAX_GROUPS];
+    float* dW[ERD_MAX_GROUPS];
+    float* rowdot[ERD_MAX_GROUPS];
+} erd_wgrad_reduce_groups;
+int erd_wgrad_reduce_grouped(const float* part, int nsplit, int Cout, int K, const erd_wgrad_reduce_groups* groups,
+                             int accumulate, erd_stream_t stream);
 
 /* dst[ci][t'][co] = rowscale[co] * w[co][t][ci]  (t' = flip ? ntaps-1-t : t): weights of the
  * input-gradient convolution. */
