@@ -201,23 +201,50 @@ def test_tower_layer_with_groupnorm_statistics_from_the_producer(K, sizes, N):
     the (sum, sum of squares) of every item's 16 groups, a tiny launch folds them to (mean, 1 / std) -- erd_wino_conv3x3_x3_gn -- and
     erd_gn_relu_apply normalises.  Against the three-pass form (conv, statistics pass, finalize, apply) on the same input: the convolution output bit for bit,
     mean / rstd and the normalised output to 1e-6 (another summation order of the same fp32 values, f64 accumulation on both sides),
-    and the statistics against an fp64 evaluation of the convolution output itself."""
+    and the statistics against an fp64 evaluation of the convolution output itself.
+    The fused form needs the 128-couts-per-item kernel.  The full-size list gets it by the launch's own choice; the small list (about
+    51 blocks: one dispatch round either way, so the launch would pick items of 64 and the wrapper the three-pass form) runs under
+    ERD_WINO_P=2.  Both assert that the fused call is fused: the library reports a partial-sum workspace for it."""
+    import os
+    from erd_amd import _lib
+    from erd_amd._lib import ConvSeg
     Cc = 256
     A = sum(h * w for h, w in sizes)
     x = G.randn(81, N, A, Cc).cuda()
     w = (G.randn(82, Cc, 3, 3, Cc) * (2.0 / (9 * Cc)) ** 0.5).cuda()
     gamma, beta = (0.5 + G.rand(83, Cc)).cuda(), G.randn(84, Cc, scale=0.3).cuda()
-    keep = K.GN_FUSED
+    keep, keep_p = K.GN_FUSED, os.environ.get("ERD_WINO_P")
     try:
+        if A < 10000:
+            os.environ["ERD_WINO_P"] = "2"
+        xs, outs = K.level_views(x, sizes), K.level_views(torch.empty_like(x), sizes)
+        segs = (ConvSeg * len(xs))()
+        for i, (a, b) in enumerate(zip(xs, outs)):
+            K._fill_seg(segs[i], a, b, a.shape[1], a.shape[2], None, None, None)
+        ws_bytes = int(_lib.load().erd_wino_x3_gn_ws_bytes(segs, len(xs), Cc))
+        assert ws_bytes > 0, "the fused call would run the three-pass form"
         K.GN_FUSED = True
+        K.workspace("gn_part", ws_bytes, x.device).view(torch.float32).fill_(float("nan"))
         c1, y1, mr1 = K.conv3x3_gn_relu_forward(x, w, gamma, beta, sizes)
+        # the fused call wrote the partial sums of every item, the three-pass form below does not touch them
+        part = K.workspace("gn_part", ws_bytes, x.device)[:ws_bytes].view(torch.float32).clone()
+        assert not bool(torch.isnan(part).any())
         K.GN_FUSED = False
         c0, y0, mr0 = K.conv3x3_gn_relu_forward(x, w, gamma, beta, sizes)
+        assert torch.equal(K.workspace("gn_part", ws_bytes, x.device)[:ws_bytes].view(torch.float32), part)
     finally:
         K.GN_FUSED = keep
+        if keep_p is None:
+            os.environ.pop("ERD_WINO_P", None)
+        else:
+            os.environ["ERD_WINO_P"] = keep_p
     torch.cuda.synchronize()
+    print(f"tower layer {sizes} N={N}: fused statistics from {ws_bytes // 128} items of 128 output channels")
     assert torch.equal(c1, c0)
     assert relerr(mr1.cpu(), mr0.cpu()) < 1e-6, relerr(mr1.cpu(), mr0.cpu())
+    for l in range(len(sizes)):             # per level: a small level is not measured against a large level's values
+        e = relerr(mr1[:, l].cpu(), mr0[:, l].cpu())
+        assert e < 1e-6, (l, e)
     assert float((y1 - y0).abs().max()) < 1e-5 * float(y0.abs().max())
     off = 0
     cd = c0.double().cpu()
