@@ -3,7 +3,10 @@ against (a) the F8 fixture produced by the reference's GFLHead.predict_by_feat a
 on seeded inputs: threshold, per-level top-k, ties, empty levels, rescale, size filter, NMS, max_per_img.
 
 Labels and the detection set must match exactly; scores within 1e-6, boxes within 1e-3 px (GPU expf vs the host's).
-Two detections whose scores differ by less than 2e-7 may swap places (the reference's sort is unstable anyway)."""
+Two detections whose scores differ by less than 2e-7 may swap places (the reference's sort is unstable anyway).
+
+The exact pins of the same kernels -- selection paths, tie order, decoded boxes and the NMS bit for bit at the C ABI, on quantised
+logits that do not depend on expf -- are in tests/test_gpu_predict_exact.py."""
 import numpy as np
 import pytest
 import torch
