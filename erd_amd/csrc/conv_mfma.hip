@@ -225,10 +225,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
     // chunk of the work list, so that the N-tiles of one pixel tile and spatially adjacent pixel tiles (3x3 halo)
     // hit the same L2 instead of being fetched through the fabric by up to 8 of them.  Bijective for any G.
     int wg = blockIdx.x;
-    if (ws.xcd_order) {
-        const int q = G >> 3, r = G & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    if (ws.xcd_order) wg = erd::xcd_contiguous(blockIdx.x, G);
     const long long u_begin = ws.whole_tiles ? ((long long)total_tiles * wg / G) * nkt : (U * wg) / G;
     const long long u_end = ws.whole_tiles ? ((long long)total_tiles * (wg + 1) / G) * nkt : (U * (wg + 1)) / G;
 
@@ -1042,6 +1039,199 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
 }
 
 // -------------------------------------------------------------------------------------------------
+// Shared by the four weight-gradient kernels below: which piece of work a workgroup has, where unit u of the concatenated K axis lies,
+// the buffer resources, the accumulators' start and the two forms of the partial-slab store.  The K loops (fragment reads, limb splits,
+// MFMA order) are each kernel's own.
+// -------------------------------------------------------------------------------------------------
+// The concatenated K axis: segments, images, rows and a row's UNITS follow each other without gaps.  A unit is a pixel (one tap per
+// workgroup) or a 16-column chunk of a row (CHUNKS: three taps per workgroup).
+template <bool CHUNKS>
+__device__ __forceinline__ int wgrad_row_units(const erd_wgrad_seg& g) { return CHUNKS ? (g.GW + 15) / 16 : g.GW; }
+__device__ __forceinline__ int wgrad_pixels(const erd_wgrad_desc& p) {
+    int P = 0;
+    for (int l = 0; l < p.nseg; ++l) P += p.seg[l].N * p.seg[l].GH * p.seg[l].GW;
+    return P;
+}
+
+// One workgroup's work: a (tap | kernel row, ci tile, co tile) of one K split.  The 1-D grid lists, fastest first, the ci tiles, the
+// taps (NTB of them: ntaps, or 3 kernel rows), the co tiles and the splits (GROUPED: of every group in turn, erd_wgrad_desc::ngroups):
+// consecutive workgroups read the same dz / x slices.
+struct WgradWork {
+    int tap, ci0, co0;          // tap index (three taps per workgroup: kernel row ky) and the first channels of the tile
+    int slab, grp;              // partial slab the workgroup writes; group whose maps it reads (0 unless GROUPED)
+    int kt_begin, kt_end;       // its K-slices: split s of a launch (or group) takes slices [s * per, (s + 1) * per), per = ceil(n / nsplit)
+    int pixels;                 // pixels of all maps (PIXELS_PER_SLICE > 0 only)
+};
+// PIXELS_PER_SLICE > 0: a slice is that many pixels of the axis and `nslices` is worked out here; 0: the launcher counted the slices
+template <int BM, int BN, int PIXELS_PER_SLICE = 0, bool GROUPED = false>
+__device__ __forceinline__ WgradWork wgrad_work(const erd_wgrad_desc& p, int ntb, int nslices, bool xcd_order) {
+    const int nci = (p.Cin + BN - 1) / BN, nco = (p.Cout + BM - 1) / BM;
+    int wg = blockIdx.x;
+    if (xcd_order) wg = erd::xcd_contiguous(blockIdx.x, gridDim.x);
+    const int nxb = nci * ntb;
+    const int bx = wg % nxb, by = (wg / nxb) % nco, bz = wg / (nxb * nco);
+    WgradWork w;
+    w.tap = bx / nci;
+    w.ci0 = (bx % nci) * BN;
+    w.co0 = by * BM;
+    w.slab = bz;
+    w.grp = GROUPED && p.ngroups > 1 ? bz / p.nsplit : 0;
+    w.pixels = 0;
+    if constexpr (PIXELS_PER_SLICE > 0) {
+        w.pixels = wgrad_pixels(p);
+        nslices = (w.pixels + PIXELS_PER_SLICE - 1) / PIXELS_PER_SLICE;
+    }
+    const int per = (nslices + p.nsplit - 1) / p.nsplit;
+    w.kt_begin = (bz - w.grp * p.nsplit) * per;
+    w.kt_end = min(nslices, w.kt_begin + per);
+    return w;
+}
+
+struct WgradUnit {
+    int l;                          // segment
+    const erd_wgrad_seg& g;         // = p.seg[l]
+    int n, a, b;                    // image, row, unit of the row
+};
+template <bool CHUNKS>
+__device__ __forceinline__ WgradUnit wgrad_locate(const erd_wgrad_desc& p, int u) {      // u < units of all maps; the only divisions
+    int l = 0;
+#pragma unroll 1
+    for (; l < p.nseg - 1; ++l) {
+        const int cnt = p.seg[l].N * p.seg[l].GH * wgrad_row_units<CHUNKS>(p.seg[l]);
+        if (u < cnt) break;
+        u -= cnt;
+    }
+    const erd_wgrad_seg& g = p.seg[l];
+    const int U = wgrad_row_units<CHUNKS>(g), GHU = g.GH * U;
+    const int n = u / GHU;
+    const int rem = u - n * GHU;
+    const int a = rem / U;
+    return {l, g, n, a, rem - a * U};
+}
+// Element offsets, image n of map g: of output pixel (oh, ow) in dz, and of input pixel (ih, iw) in x -- `ox` keeps its value (the
+// caller's mark of a zero row) where that pixel is padding
+__device__ __forceinline__ int wgrad_dz_offset(const erd_wgrad_desc& p, const erd_wgrad_seg& g, int n, int oh, int ow) {
+    return (int)(g.dz_off + n * g.dz_nstride) + (oh * g.OW + ow) * p.Cout;
+}
+__device__ __forceinline__ void wgrad_x_offset(const erd_wgrad_desc& p, const erd_wgrad_seg& g, int n, int ih, int iw, int& ox) {
+    if ((unsigned)ih < (unsigned)g.IH && (unsigned)iw < (unsigned)g.IW) ox = (int)(g.x_off + n * g.x_nstride) + (ih * g.IW + iw) * p.Cin;
+}
+// (oz, ox) of pixel (a, b) of the gradient map under a tap that reads (dyt, dxt) away: the strided form of the one-tap kernels.  (The two
+// three-tap kernels keep their halo forms, and the three-limb kernel its byte offsets, in their own K loops: see there.)
+__device__ __forceinline__ void wgrad_tap_offsets(const erd_wgrad_desc& p, const erd_wgrad_seg& g, int n, int a, int b, int dyt, int dxt, int& oz,
+                                                  int& ox) {
+    oz = wgrad_dz_offset(p, g, n, a * p.out_stride + p.oy, b * p.out_stride + p.ox);
+    wgrad_x_offset(p, g, n, a * p.in_stride + dyt, b * p.in_stride + dxt, ox);
+}
+
+struct WgradRsrc { __amdgpu_buffer_rsrc_t dz, x; };
+__device__ __forceinline__ WgradRsrc wgrad_rsrc(const erd_wgrad_desc& p, const void* dz, const void* x, int dz_bytes = 4, int x_bytes = 4) {
+    return {__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(dz), 0, (int)(p.dz_elems * dz_bytes), 0x00020000),
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(x), 0, (int)(p.x_elems * x_bytes), 0x00020000)};
+}
+
+template <int NACC>
+__device__ __forceinline__ void wgrad_zero(f32x16* acc) {
+#pragma unroll
+    for (int i = 0; i < NACC; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+}
+
+// Where a wave's accumulators go: wave (wm, wn) owns FM x FN 32x32 blocks, lane (li, h) of block (i, j) holds column (wn * FN + j) * 32 + li
+// and, in register r, row wgrad_acc_row((wm * FM + i) * 32, r, h) of the workgroup's tile.
+struct WgradLane { int wm, wn, li, h; };
+__device__ __forceinline__ int wgrad_acc_row(int block_row, int r, int h) { return block_row + (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// Partial slab [Cout][ntaps][Cin], taps tap0 .. tap0 + NT - 1 of it from acc[NT][FM][FN], DIRECT: one float per lane and store (the
+// fp32-MFMA kernels)
+template <int NT, int FM, int FN>
+__device__ __forceinline__ void wgrad_store_direct(float* __restrict__ part, const f32x16* acc, const erd_wgrad_desc& p, int ntaps, int tap0,
+                                                   int co0, int ci0, const WgradLane& w) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+            const int ci = ci0 + (w.wn * FN + j) * 32 + w.li;
+            if (ci >= p.Cin) continue;
+#pragma unroll
+            for (int i = 0; i < FM; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = wgrad_acc_row(co0 + (w.wm * FM + i) * 32, r, w.h);
+                    if (co < p.Cout) part[((int64_t)co * ntaps + tap0 + t) * p.Cin + ci] = acc[(t * FM + i) * FN + j][r];
+                }
+        }
+}
+
+// ... STAGED through the idle operand LDS (`stage`, LDS_BYTES of it), as many accumulator rows per pass as fit: the accumulators'
+// one-float-per-lane layout would be 16 x FM x FN four-byte stores per lane (8 % of a three-limb launch); staged, every thread writes
+// whole 16-byte pieces of slab rows.  Q > 0: the kernel keeps channel 4 (r % Q) + r / Q of an operand in LDS row r (QA: dz rows, QB: x
+// rows), undone here; 0: channels in order.  16-byte pieces need Cin % 4 == 0: erd_conv_wgrad refuses every other descriptor.
+template <int Q>
+__device__ __forceinline__ int wgrad_row_channel(int row) {
+    if constexpr (Q > 0) return 4 * (row % Q) + row / Q;
+    else return row;
+}
+template <int FM, int FN, int LDS_BYTES, int QA, int QB>
+__device__ __forceinline__ void wgrad_store_staged(float* stage, float* __restrict__ part, const f32x16 (&acc)[FM][FN], const erd_wgrad_desc& p,
+                                                   int ntaps, int tap, int co0, int ci0, const WgradLane& w, int tid) {
+    constexpr int BMR = 2 * FM * 32, BNR = 2 * FN * 32;                      // the tile of 2 x 2 waves
+    constexpr int SLDW = BNR + 4;                                            // floats per staged row
+    constexpr int RPASS = (BMR * SLDW * 4 <= LDS_BYTES) ? BMR : BMR / 2;     // accumulator rows per pass
+    constexpr int NPASS = BMR / RPASS, C4 = BNR / 4;
+    static_assert(RPASS * SLDW * 4 <= LDS_BYTES && RPASS % 32 == 0, "slab staging");
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps) {
+        __syncthreads();               // the K loop's fragment reads / the previous pass are done with the operand buffers
+#pragma unroll
+        for (int i = 0; i < FM; ++i) {
+            if (((w.wm * FM + i) * 32) / RPASS != ps) continue;              // (wave-uniform)
+#pragma unroll
+            for (int j = 0; j < FN; ++j) {
+                const int col = wgrad_row_channel<QB>((w.wn * FN + j) * 32 + w.li);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int arow = wgrad_acc_row((w.wm * FM + i) * 32, r, w.h);
+                    stage[(arow - ps * RPASS) * SLDW + col] = acc[i][j][r];
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < RPASS * C4 / NTHREADS; ++q) {
+            const int idx = q * NTHREADS + tid;
+            const int row = idx / C4, c4 = idx - row * C4;
+            const int co = co0 + wgrad_row_channel<QA>(ps * RPASS + row), ci = ci0 + 4 * c4;
+            if (co < p.Cout && ci < p.Cin)
+                *reinterpret_cast<float4*>(part + ((int64_t)co * ntaps + tap) * p.Cin + ci) =
+                    *reinterpret_cast<const float4*>(stage + row * SLDW + 4 * c4);
+        }
+    }
+}
+
+// Dynamic LDS of each kernel, from the constants the kernel carves it with (erd_conv_wgrad asks these for the launch's byte count)
+template <int BM, int BN, int BK, int BX = BK>      // fp32 MFMA: k-major tiles [2][BK][BM] dz, [2][BX][BN] x (BX: with the halo)
+struct WgradF32Lds {
+    static constexpr int A_FLOATS = 2 * BK * BM, B_FLOATS = 2 * BX * BN;
+    static constexpr size_t BYTES = (size_t)(A_FLOATS + B_FLOATS) * sizeof(float) + 2 * (BK + BX) * sizeof(int);      // + offsets [2][BK], [2][BX]
+};
+template <int FM, int FN, bool ROW3>      // three-limb form: [2 buffers][3 planes] of channel-major rows, and a ring of NSLOT table slots
+struct WgradX3Lds {
+    static constexpr int BK = 16, BX = ROW3 ? BK + 2 : BK, BMR = FM * 64, BNR = FN * 64;
+    static constexpr int A_ROWB = 32, B_ROWB = ROW3 ? 48 : 32;       // bytes per LDS row of one plane
+    static constexpr int A_PL = BMR * A_ROWB, B_PL = BNR * B_ROWB;   // bytes per plane
+    static constexpr int BUF = 3 * (A_PL + B_PL);
+    static constexpr int TB = (BX + 3) / 4 * 4, NSLOT = 8;           // x table entries per slot (whole groups of four), slots of the ring
+    static constexpr size_t BYTES = (size_t)2 * BUF + NSLOT * (BK + TB) * sizeof(unsigned);
+};
+struct WgradBf16Lds {                       // bf16 MFMA: [2][128 rows][8 chunks of 16 B] per operand, offsets [2][BK]
+    static constexpr int BM = 128, BN = 128, BK = 64;
+    static constexpr int A_VEC = 2 * BM * 8, B_VEC = 2 * BN * 8;
+    static constexpr size_t OPERAND_BYTES = (size_t)(A_VEC + B_VEC) * sizeof(float4), BYTES = OPERAND_BYTES + 2 * BK * sizeof(int2);
+};
+
+// -------------------------------------------------------------------------------------------------
 // weight gradient: G[co][t][ci] = sum_p dz[p][co] * x[p+tap t][ci]; K = pixels (split over gridDim.z)
 // LDS tiles are k-major ([32 px][128 ch], exactly the global layout); fragments by ds_read_b32.
 // -------------------------------------------------------------------------------------------------
@@ -1053,34 +1243,15 @@ __global__ __launch_bounds__(NTHREADS, MINW) void conv_wgrad_kernel(const erd_wg
     constexpr int AJ = (BK * AC) / NTHREADS, BJ = (BK * BC) / NTHREADS;
     constexpr int AR = NTHREADS / AC, BR = NTHREADS / BC;  // rows covered per pass
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    using L = WgradF32Lds<BM, BN, BK>;
     float* As = reinterpret_cast<float*>(smem);   // [2][BK][BM]
-    float* Bs = As + 2 * BK * BM;                 // [2][BK][BN]
-    int2* offs = reinterpret_cast<int2*>(Bs + 2 * BK * BN);   // [2][BK]: (dz offset, x offset) per pixel, -1 = zero row
+    float* Bs = As + L::A_FLOATS;                 // [2][BK][BN]
+    int2* offs = reinterpret_cast<int2*>(Bs + L::B_FLOATS);   // [2][BK]: (dz offset, x offset) per pixel, -1 = zero row
 
     const int tid = threadIdx.x;
-    const int nci = (p.Cin + BN - 1) / BN;
-    // 1-D grid; consecutive workgroups = the (tap, ci-tile, co-tile) combinations of one pixel range (split).  Left in
-    // dispatch order (spread over the 8 XCDs): pinning a split to one XCD's L2 measured 3-20 % SLOWER here (36
-    // workgroups hammering the same L2 lines), unlike the igemm kernel (ERD_XCD=2 re-enables it for A/B runs).
-    int wg = blockIdx.x;
-    if (xcd_order) {
-        const int G = gridDim.x, q = G >> 3, r = G & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int nxb = nci * p.ntaps, nyb = (p.Cout + BM - 1) / BM;
-    const int bx = wg % nxb, by = (wg / nxb) % nyb, bz = wg / (nxb * nyb);
-    const int tap = bx / nci;
-    const int ci0 = (bx % nci) * BN;
-    const int co0 = by * BM;
-    int P = 0;
-    for (int l = 0; l < p.nseg; ++l) P += p.seg[l].N * p.seg[l].GH * p.seg[l].GW;
-    const int nkt_total = (P + BK - 1) / BK;
-    const int per = (nkt_total + p.nsplit - 1) / p.nsplit;
-    const int kt_begin = bz * per;
-    const int kt_end = min(nkt_total, kt_begin + per);
+    const WgradWork wk = wgrad_work<BM, BN, BK>(p, p.ntaps, 0, xcd_order);
+    const int tap = wk.tap, ci0 = wk.ci0, co0 = wk.co0, kt_begin = wk.kt_begin, kt_end = wk.kt_end, P = wk.pixels;
     const int dyt = p.dy[tap], dxt = p.dx[tap];
-    const float* __restrict__ x = p.x;
-    const float* __restrict__ dz = p.dz;
 
     const int achunk = tid % AC, ar0 = tid / AC;
     const int bchunk = tid % BC, br0 = tid / BC;
@@ -1088,39 +1259,21 @@ __global__ __launch_bounds__(NTHREADS, MINW) void conv_wgrad_kernel(const erd_wg
     const bool b_cok = ci0 + bchunk * 4 < p.Cin;
     const int a_col = co0 + achunk * 4, b_col = ci0 + bchunk * 4;
 
-    // pixel -> element offsets of one K-slice, computed once by 32 threads (the divisions live here only)
+    // pixel -> element offsets of one K-slice, computed once by BK threads (the divisions live here only)
     auto compute_offsets = [&](int kt, int slot) {
         if (tid < BK) {
-            int pp = kt * BK + tid;
-            int2 o = make_int2(-1, -1);
+            const int pp = kt * BK + tid;
+            int oz = -1, ox = -1;
             if (pp < P && kt < kt_end) {
-                int l = 0;
-#pragma unroll 1
-                for (; l < p.nseg - 1; ++l) {      // which map does this pixel of the concatenated K axis belong to
-                    const int pl = p.seg[l].N * p.seg[l].GH * p.seg[l].GW;
-                    if (pp < pl) break;
-                    pp -= pl;
-                }
-                const erd_wgrad_seg& g = p.seg[l];
-                const int GHW = g.GH * g.GW;
-                const int n = pp / GHW;
-                const int rem = pp - n * GHW;
-                const int a = rem / g.GW;
-                const int b = rem - a * g.GW;
-                o.x = (int)(g.dz_off + n * g.dz_nstride) +
-                      ((a * p.out_stride + p.oy) * g.OW + (b * p.out_stride + p.ox)) * p.Cout;
-                const int ih = a * p.in_stride + dyt, iw = b * p.in_stride + dxt;
-                if ((unsigned)ih < (unsigned)g.IH && (unsigned)iw < (unsigned)g.IW)
-                    o.y = (int)(g.x_off + n * g.x_nstride) + (ih * g.IW + iw) * p.Cin;
+                const WgradUnit u = wgrad_locate<false>(p, pp);
+                wgrad_tap_offsets(p, u.g, u.n, u.a, u.b, dyt, dxt, oz, ox);
             }
-            offs[slot * BK + tid] = o;
+            offs[slot * BK + tid] = make_int2(oz, ox);
         }
     };
 
-    const __amdgpu_buffer_rsrc_t rs_dz = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(dz), 0, (int)(p.dz_elems * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(x), 0, (int)(p.x_elems * 4), 0x00020000);
+    const WgradRsrc rs = wgrad_rsrc(p, p.dz, p.x);
+    const __amdgpu_buffer_rsrc_t rs_dz = rs.dz, rs_x = rs.x;
     float4 ra[AJ], rb[BJ];
     auto load_global = [&](int slot) {   // branch-free: zero rows come from the buffer's out-of-range rule
 #pragma unroll
@@ -1147,12 +1300,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void conv_wgrad_kernel(const erd_wg
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, h = lane >> 5;
     f32x16 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    wgrad_zero<FM * FN>(&acc[0][0]);
 
     if (kt_begin < kt_end) {
         compute_offsets(kt_begin, 0);
@@ -1187,19 +1335,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void conv_wgrad_kernel(const erd_wg
         }
     }
     // partial slab [z][Cout][ntaps][Cin]
-    float* __restrict__ part = p.part + (int64_t)bz * p.Cout * p.ntaps * p.Cin;
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-        const int ci = ci0 + (wn * FN + j) * 32 + li;
-        if (ci >= p.Cin) continue;
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = co0 + (wm * FM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (co < p.Cout) part[((int64_t)co * p.ntaps + tap) * p.Cin + ci] = acc[i][j][r];
-            }
-    }
+    wgrad_store_direct<1, FM, FN>(p.part + (int64_t)wk.slab * p.Cout * p.ntaps * p.Cin, &acc[0][0], p, p.ntaps, tap, co0, ci0, WgradLane{wm, wn, li, h});
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1220,30 +1356,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_row3_kernel(const erd_
     constexpr int WAVES_N = 4 / WAVES_M, BME = WAVES_M * FM * 32;
     static_assert(WAVES_N * FN * 32 == BN && BME <= BM, "wave tiling");
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    using L = WgradF32Lds<BM, BN, BK, BX>;
     float* As = reinterpret_cast<float*>(smem);        // [2][BK][BM]   dz
-    float* Bs = As + 2 * BK * BM;                      // [2][BX][BN]   x with halo
-    int* offa = reinterpret_cast<int*>(Bs + 2 * BX * BN);   // [2][BK] dz element offsets (-1: zero row)
+    float* Bs = As + L::A_FLOATS;                      // [2][BX][BN]   x with halo
+    int* offa = reinterpret_cast<int*>(Bs + L::B_FLOATS);   // [2][BK] dz element offsets (-1: zero row)
     int* offb = offa + 2 * BK;                         // [2][BX] x element offsets (-1: zero row)
 
     const int tid = threadIdx.x;
-    const int nci = (p.Cin + BN - 1) / BN, nco = (p.Cout + BME - 1) / BME;
-    // The (cin block, kernel row, cout block) workgroups of one K split read the same dz / x slices.  Workgroup b runs on XCD
-    // b % 8 (each XCD has its own L2): give every XCD a CONTIGUOUS range of the work list so that the siblings of a split
-    // share one L2 instead of pulling the slices through the fabric up to eight times.
-    int wg = blockIdx.x;
-    if (nslices_xcd >> 30) {
-        const int G = gridDim.x, q = G >> 3, r = G & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int bx = wg % (nci * 3), by = (wg / (nci * 3)) % nco, bz = wg / (nci * 3 * nco);
-    const int ky = bx / nci;
-    const int ci0 = (bx % nci) * BN;
-    const int co0 = by * BME;
-    const int per = (nslices + p.nsplit - 1) / p.nsplit;
-    const int kt_begin = bz * per;
-    const int kt_end = min(nslices, kt_begin + per);
-    const float* __restrict__ x = p.x;
-    const float* __restrict__ dz = p.dz;
+    // The (cin block, kernel row, cout block) workgroups of one K split read the same dz / x slices: in the XCD-contiguous order the
+    // siblings of a split share one L2 instead of pulling the slices through the fabric up to eight times.
+    const WgradWork wk = wgrad_work<BME, BN>(p, 3, nslices, nslices_xcd >> 30);
+    const int ky = wk.tap, ci0 = wk.ci0, co0 = wk.co0, kt_begin = wk.kt_begin, kt_end = wk.kt_end;
 
     const int chunk = tid & 31, r0 = tid >> 5;          // 32 float4 chunks per 128-channel row, 8 rows per pass
     const bool a_cok = chunk * 4 < BME && co0 + chunk * 4 < p.Cout;
@@ -1255,6 +1378,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_row3_kernel(const erd_
         if (tid < BX) {
             int oa = -1, ob = -1;
             if (kt < kt_end) {
+                // (this kernel's own decode -- row chunk first, then row and image -- and offset formulas: through wgrad_locate /
+                //  wgrad_x_offset the compiler arranges this K loop differently, and the loop is pinned instruction for instruction)
                 int l = 0, q = kt;
 #pragma unroll 1
                 for (; l < p.nseg - 1; ++l) {
@@ -1279,10 +1404,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_row3_kernel(const erd_
         }
     };
 
-    const __amdgpu_buffer_rsrc_t rs_dz = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(dz), 0, (int)(p.dz_elems * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(x), 0, (int)(p.x_elems * 4), 0x00020000);
+    const WgradRsrc rs = wgrad_rsrc(p, p.dz, p.x);
+    const __amdgpu_buffer_rsrc_t rs_dz = rs.dz, rs_x = rs.x;
     float4 ra[2], rb[2], rh;
     auto load_global = [&](int slot) {
 #pragma unroll
@@ -1314,14 +1437,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_row3_kernel(const erd_
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int li = lane & 31, h = lane >> 5;
     f32x16 acc[3][FM][FN];
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[t][i][j][r] = 0.f;
+    wgrad_zero<3 * FM * FN>(&acc[0][0][0]);
 
     if (kt_begin < kt_end) {
         compute_offsets(kt_begin, 0);
@@ -1367,21 +1483,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_row3_kernel(const erd_
             __syncthreads();
         }
     }
-    float* __restrict__ part = p.part + (int64_t)bz * p.Cout * 9 * p.Cin;
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-            const int ci = ci0 + (wn * FN + j) * 32 + li;
-            if (ci >= p.Cin) continue;
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = co0 + (wm * FM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (co < p.Cout) part[((int64_t)co * 9 + ky * 3 + t) * p.Cin + ci] = acc[t][i][j][r];
-                }
-        }
+    wgrad_store_direct<3, FM, FN>(p.part + (int64_t)wk.slab * p.Cout * 9 * p.Cin, &acc[0][0][0], p, 9, ky * 3, co0, ci0, WgradLane{wm, wn, li, h});
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1409,38 +1511,25 @@ template <int FM, int FN, bool ROW3>
 __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_kernel(const erd_wgrad_desc p, const int nslices_xcd) {
     const int nslices = nslices_xcd & 0x3fffffff;
     constexpr int NT = ROW3 ? 3 : 1;
-    constexpr int BK = 16, BX = ROW3 ? BK + 2 : BK, BMR = FM * 64, BNR = FN * 64;
-    constexpr int A_ROWB = 32, B_ROWB = ROW3 ? 48 : 32;        // bytes per LDS row of one plane
-    constexpr int A_PL = BMR * A_ROWB, B_PL = BNR * B_ROWB;    // bytes per plane
-    constexpr int BUF = 3 * (A_PL + B_PL);
+    using L = WgradX3Lds<FM, FN, ROW3>;
+    constexpr int BK = L::BK, BX = L::BX, BMR = L::BMR, BNR = L::BNR;
+    constexpr int A_ROWB = L::A_ROWB, B_ROWB = L::B_ROWB, A_PL = L::A_PL, B_PL = L::B_PL, BUF = L::BUF;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // Offset tables: FINAL byte offsets of a slice's pixels (the loading thread adds its constant channel term), TAB_INV for a pixel
     // that does not exist (padding, past the end) -- with the channel term added it stays past the extent of any buffer we build
     // (extents are below 2^31 bytes, erd_conv_wgrad).  A thread reads its four entries as ONE 16-byte LDS load, so a slot of the x
     // table is padded to whole groups of four (three taps: 18 -> 20 entries).  A ring of 8 slots, filled four slices per pass.
-    constexpr int TB = (BX + 3) / 4 * 4, NSLOT = 8;
+    constexpr int TB = L::TB, NSLOT = L::NSLOT;
     constexpr unsigned TAB_INV = 0x80000000u;
     unsigned* offa = reinterpret_cast<unsigned*>(smem + 2 * BUF);      // [NSLOT][BK]
     unsigned* offb = offa + NSLOT * BK;                                // [NSLOT][TB]
 
     const int tid = threadIdx.x;
-    const int nci = (p.Cin + BNR - 1) / BNR, nco = (p.Cout + BMR - 1) / BMR;
-    int wg = blockIdx.x;
-    if (nslices_xcd >> 30) {
-        const int G = gridDim.x, q = G >> 3, r = G & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int nbx = nci * (ROW3 ? 3 : p.ntaps);
-    const int bx = wg % nbx, by = (wg / nbx) % nco, bz = wg / (nbx * nco);
-    const int ky = bx / nci;                                   // ROW3: kernel row; otherwise the tap index
-    const int ci0 = (bx % nci) * BNR;
-    const int co0 = by * BMR;
-    // grouped launch (erd_wgrad_desc::ngroups > 1): split bz is local split bz % nsplit of group bz / nsplit -- the K range, the tables
-    // and the walker are those of a launch of that group alone, only the two base pointers (below) and the slab index bz differ
-    const int grp = p.ngroups > 1 ? bz / p.nsplit : 0;
-    const int per = (nslices + p.nsplit - 1) / p.nsplit;
-    const int kt_begin = (bz - grp * p.nsplit) * per;
-    const int kt_end = min(nslices, kt_begin + per);
+    // grouped launch (erd_wgrad_desc::ngroups > 1): slab s is local split s % nsplit of group s / nsplit -- the K range, the tables
+    // and the walker are those of a launch of that group alone, only the two base pointers (below) and the slab index differ
+    const WgradWork wk = wgrad_work<BMR, BNR, 0, true>(p, ROW3 ? 3 : p.ntaps, nslices, nslices_xcd >> 30);
+    const int ky = wk.tap;                                     // ROW3: kernel row; otherwise the tap index
+    const int ci0 = wk.ci0, co0 = wk.co0, grp = wk.grp, kt_begin = wk.kt_begin, kt_end = wk.kt_end;
 
     const int wave = tid >> 6, lane = tid & 63;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // (the compiler cannot see that tid >> 6 is the same in all lanes)
@@ -1453,29 +1542,17 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
     // image of the first one (a pass that straddles an image or segment boundary, or the end of the axis) and, with one tap, every lane
     // of a map narrower than 16 pixels (many wraps) decodes its unit index itself.
     constexpr int UPS = ROW3 ? 1 : BK;                         // units per slice
-    auto row_units = [&](const erd_wgrad_seg& g) { return ROW3 ? (g.GW + BK - 1) / BK : g.GW; };
-    int P = nslices, sl = 0, sn = 0, sa = 0, sb = 0;         // P: units of all maps
-    if (!ROW3) {
-        P = 0;
-        for (int l = 0; l < p.nseg; ++l) P += p.seg[l].N * p.seg[l].GH * p.seg[l].GW;
-    }
-    {
-        int q = kt_begin * UPS;
-        for (; sl < p.nseg; ++sl) {
-            const int pl = p.seg[sl].N * p.seg[sl].GH * row_units(p.seg[sl]);
-            if (q < pl) break;
-            q -= pl;
-        }
-        if (sl < p.nseg) {
-            const int U = row_units(p.seg[sl]), GHU = p.seg[sl].GH * U;
-            sn = q / GHU;
-            q -= sn * GHU;
-            sa = q / U;
-            sb = q - sa * U;
-        }
+    auto row_units = [&](const erd_wgrad_seg& g) { return wgrad_row_units<ROW3>(g); };
+    const int P = ROW3 ? nslices : wgrad_pixels(p);          // units of all maps
+    int sl = p.nseg, sn = 0, sa = 0, sb = 0;                 // (an empty split past the end of the axis: no segment)
+    if (kt_begin * UPS < P) {
+        const WgradUnit u = wgrad_locate<ROW3>(p, kt_begin * UPS);
+        sl = u.l; sn = u.n; sa = u.a; sb = u.b;
     }
     // offsets of unit b of row a of image n of map g: dz pixel `oa` and x entry `ob` of the lane (three taps: entry e is column
-    // 16 b + e - 1 of row a + ky - 1; lanes e < 4 also have entry 16 + e, of which 18 and 19 pad the slot)
+    // 16 b + e - 1 of row a + ky - 1; lanes e < 4 also have entry 16 + e, of which 18 and 19 pad the slot).  BYTE offsets with TAB_INV for a
+    // missing pixel, written out here: through wgrad_tap_offsets the compiler merges the walked and the per-lane path of table_pass and
+    // fetches the walked path's segment fields with vector loads instead of scalar ones
     auto unit_offsets = [&](const erd_wgrad_seg& g, int n, int a, int b, unsigned& oa, unsigned& ob, unsigned& ob2) {
         if constexpr (ROW3) {
             const int e = lane & 15, zcol = b * BK + e, ih = a + ky - 1;
@@ -1512,21 +1589,10 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
             }
             if (walked) unit_offsets(g, sn, a, b, oa, ob, ob2);
             else {
-                int pp = ks * UPS + u;
+                const int pp = ks * UPS + u;
                 if (pp < P) {
-                    int l = 0;
-#pragma unroll 1
-                    for (; l < p.nseg - 1; ++l) {
-                        const int pl = p.seg[l].N * p.seg[l].GH * row_units(p.seg[l]);
-                        if (pp < pl) break;
-                        pp -= pl;
-                    }
-                    const erd_wgrad_seg& gl = p.seg[l];
-                    const int Ul = row_units(gl), GHU = gl.GH * Ul;
-                    const int n = pp / GHU;
-                    const int rem = pp - n * GHU;
-                    const int al = rem / Ul;
-                    unit_offsets(gl, n, al, rem - al * Ul, oa, ob, ob2);
+                    const WgradUnit w = wgrad_locate<ROW3>(p, pp);
+                    unit_offsets(w.g, w.n, w.a, w.b, oa, ob, ob2);
                 }
             }
         }
@@ -1556,8 +1622,8 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
         for (int g = 0; g < ERD_MAX_GROUPS; ++g)
             if (g == grp) { base_dz = p.gdz[g]; base_x = p.gx[g]; }
     }
-    const __amdgpu_buffer_rsrc_t rs_dz = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base_dz), 0, (int)(p.dz_elems * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base_x), 0, (int)(p.x_elems * 4), 0x00020000);
+    const WgradRsrc rs = wgrad_rsrc(p, base_dz, base_x);
+    const __amdgpu_buffer_rsrc_t rs_dz = rs.dz, rs_x = rs.x;
 
     // ---- staging roles: threads [0, NA) own a dz micro-tile (4 px x 4 co), threads [128, 128 + 80) an x micro-tile (4 entries x 4 ci)
     constexpr int NA = (BMR / 4) * 4;                           // dz micro-tiles: (BMR / 4) channel groups x 4 pixel groups
@@ -1619,14 +1685,7 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, h = lane >> 5;
     f32x16 acc[NT][FM][FN];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[t][i][j][r] = 0.f;
+    wgrad_zero<NT * FM * FN>(&acc[0][0][0]);
 
     if (kt_begin < kt_end) {
         if (wave_u == 0) table_pass(kt_begin);
@@ -1702,71 +1761,14 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
             __syncthreads();
         }
     }
+    // partial slab through LDS, one tap (and at most 128 x 64 / 64 x 128 values) at a time; the (co, ci) permutations of the operand rows
+    // are undone on the way
     const int ntaps_all = ROW3 ? 9 : p.ntaps;
-    float* __restrict__ part = p.part + (int64_t)bz * p.Cout * ntaps_all * p.Cin;
-    if ((p.Cin & 3) == 0) {
-        // ---- partial slab through LDS, one tap (and at most 128 x 64 / 64 x 128 values) at a time: the accumulators' one-float-per-lane
-        // layout would be 16 x FM x FN x taps four-byte stores per lane (8 % of a launch, timing probe ERD_WG3_NOSLAB); staged, the
-        // (co, ci) permutations of the operand rows are undone on the way and every thread writes whole 16-byte pieces of slab rows
-        constexpr int SLDW = BNR + 4;                                            // floats per staged row
-        constexpr int RPASS = (BMR * SLDW * 4 <= 2 * BUF) ? BMR : BMR / 2;       // accumulator rows per pass
-        constexpr int NPASS = BMR / RPASS, C4 = BNR / 4;
-        static_assert(RPASS * SLDW * 4 <= 2 * BUF && RPASS % 32 == 0, "slab staging");
-        float* stage = reinterpret_cast<float*>(smem);
+    float* __restrict__ part = p.part + (int64_t)wk.slab * p.Cout * ntaps_all * p.Cin;
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-#pragma unroll
-            for (int ps = 0; ps < NPASS; ++ps) {
-                __syncthreads();               // the K loop's fragment reads / the previous pass are done with the operand buffers
-#pragma unroll
-                for (int i = 0; i < FM; ++i) {
-                    if (((wm * FM + i) * 32) / RPASS != ps) continue;            // (wave-uniform)
-#pragma unroll
-                    for (int j = 0; j < FN; ++j) {
-                        const int brow = (wn * FN + j) * 32 + li;                  // LDS row of the x operand -> input channel of the tile
-                        const int col = 4 * (brow % QB) + brow / QB;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int arow = (wm * FM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                            stage[(arow - ps * RPASS) * SLDW + col] = acc[t][i][j][r];
-                        }
-                    }
-                }
-                __syncthreads();
-#pragma unroll
-                for (int q = 0; q < RPASS * C4 / NTHREADS; ++q) {
-                    const int idx = q * NTHREADS + tid;
-                    const int row = idx / C4, c4 = idx - row * C4;
-                    const int arow = ps * RPASS + row;                              // LDS row of the dz operand -> output channel
-                    const int co = co0 + 4 * (arow % QA) + arow / QA, ci = ci0 + 4 * c4;
-                    if (co < p.Cout && ci < p.Cin)
-                        *reinterpret_cast<float4*>(part + ((int64_t)co * ntaps_all + (ROW3 ? ky * 3 + t : ky)) * p.Cin + ci) =
-                            *reinterpret_cast<const float4*>(stage + row * SLDW + 4 * c4);
-                }
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-        const int brow = (wn * FN + j) * 32 + li;              // LDS row of the x operand ...
-        const int ci = ci0 + 4 * (brow % QB) + brow / QB;      // ... holds this input channel
-        if (ci >= p.Cin) continue;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int arow = (wm * FM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;      // LDS row of the dz operand ...
-                    const int co = co0 + 4 * (arow % QA) + arow / QA;                          // ... holds this output channel
-#ifdef ERD_WG3_NOSLAB      // timing probe: the partial slab is not written (results are wrong; read against the build BEFORE the staged slab write)
-                    if (co < p.Cout) asm volatile("" :: "v"(acc[t][i][j][r]));
-#else
-                    if (co < p.Cout) part[((int64_t)co * ntaps_all + (ROW3 ? ky * 3 + t : ky)) * p.Cin + ci] = acc[t][i][j][r];
-#endif
-                }
-    }
+    for (int t = 0; t < NT; ++t)
+        wgrad_store_staged<FM, FN, 2 * BUF, QA, QB>(reinterpret_cast<float*>(smem), part, acc[t], p, ntaps_all, ROW3 ? ky * 3 + t : ky, co0, ci0,
+                                                    WgradLane{wm, wn, li, h}, tid);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1781,27 +1783,17 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
 // one pixel each) and the register transpose is a v_perm_b32 per pixel pair instead of a v_cvt_pk_bf16_f32.
 template <bool XB, bool DB>
 __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_bf16_kernel(const erd_wgrad_desc p) {
-    constexpr int BM = 128, BN = 128, BK = 64;          // BK pixels per K-slice = 8 chunks of 8 pixels
+    using L = WgradBf16Lds;
+    constexpr int BM = L::BM, BN = L::BN, BK = L::BK;      // BK pixels per K-slice = 8 chunks of 8 pixels
     constexpr int FM = 2, FN = 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float4* As = reinterpret_cast<float4*>(smem);          // [2][BM rows][8 chunks]
-    float4* Bs = As + 2 * BM * 8;                          // [2][BN rows][8 chunks]
-    int2* offs = reinterpret_cast<int2*>(Bs + 2 * BN * 8); // [2][BK]
+    float4* Bs = As + L::A_VEC;                            // [2][BN rows][8 chunks]
+    int2* offs = reinterpret_cast<int2*>(Bs + L::B_VEC);   // [2][BK]
 
     const int tid = threadIdx.x;
-    const int nci = (p.Cin + BN - 1) / BN;
-    const int wg = blockIdx.x;
-    const int nxb = nci * p.ntaps, nyb = (p.Cout + BM - 1) / BM;
-    const int bx = wg % nxb, by = (wg / nxb) % nyb, bz = wg / (nxb * nyb);
-    const int tap = bx / nci;
-    const int ci0 = (bx % nci) * BN;
-    const int co0 = by * BM;
-    int P = 0;
-    for (int l = 0; l < p.nseg; ++l) P += p.seg[l].N * p.seg[l].GH * p.seg[l].GW;
-    const int nkt_total = (P + BK - 1) / BK;
-    const int per = (nkt_total + p.nsplit - 1) / p.nsplit;
-    const int kt_begin = bz * per;
-    const int kt_end = min(nkt_total, kt_begin + per);
+    const WgradWork wk = wgrad_work<BM, BN, BK>(p, p.ntaps, 0, false);      // (dispatch order)
+    const int tap = wk.tap, ci0 = wk.ci0, co0 = wk.co0, kt_begin = wk.kt_begin, kt_end = wk.kt_end, P = wk.pixels;
     const int dyt = p.dy[tap], dxt = p.dx[tap];
 
     const int cc = tid & 31, pg = tid >> 5;               // 4-channel group, 8-pixel group of this thread's micro-tiles
@@ -1811,36 +1803,18 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_bf16_kernel(const erd_
 
     auto compute_offsets = [&](int kt, int slot) {
         if (tid < BK) {
-            int pp = kt * BK + tid;
-            int2 o = make_int2(-1, -1);
+            const int pp = kt * BK + tid;
+            int oz = -1, ox = -1;
             if (pp < P && kt < kt_end) {
-                int l = 0;
-#pragma unroll 1
-                for (; l < p.nseg - 1; ++l) {
-                    const int pl = p.seg[l].N * p.seg[l].GH * p.seg[l].GW;
-                    if (pp < pl) break;
-                    pp -= pl;
-                }
-                const erd_wgrad_seg& g = p.seg[l];
-                const int GHW = g.GH * g.GW;
-                const int n = pp / GHW;
-                const int rem = pp - n * GHW;
-                const int a = rem / g.GW;
-                const int b = rem - a * g.GW;
-                o.x = (int)(g.dz_off + n * g.dz_nstride) +
-                      ((a * p.out_stride + p.oy) * g.OW + (b * p.out_stride + p.ox)) * p.Cout;
-                const int ih = a * p.in_stride + dyt, iw = b * p.in_stride + dxt;
-                if ((unsigned)ih < (unsigned)g.IH && (unsigned)iw < (unsigned)g.IW)
-                    o.y = (int)(g.x_off + n * g.x_nstride) + (ih * g.IW + iw) * p.Cin;
+                const WgradUnit u = wgrad_locate<false>(p, pp);
+                wgrad_tap_offsets(p, u.g, u.n, u.a, u.b, dyt, dxt, oz, ox);
             }
-            offs[slot * BK + tid] = o;
+            offs[slot * BK + tid] = make_int2(oz, ox);
         }
     };
 
-    const __amdgpu_buffer_rsrc_t rs_dz = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.dz), 0, (int)(p.dz_elems * (DB ? 2 : 4)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x), 0, (int)(p.x_elems * (XB ? 2 : 4)), 0x00020000);
+    const WgradRsrc rs = wgrad_rsrc(p, p.dz, p.x, DB ? 2 : 4, XB ? 2 : 4);
+    const __amdgpu_buffer_rsrc_t rs_dz = rs.dz, rs_x = rs.x;
     typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     float4 ra[DB ? 1 : 8], rb[XB ? 1 : 8];          // fp32-stored operand: 4 channels of one pixel per load
     u32x2 ua[DB ? 8 : 1], ub[XB ? 8 : 1];           // bf16-stored operand: the same 4 channels in 8 bytes
@@ -1898,12 +1872,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_bf16_kernel(const erd_
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, h = lane >> 5;
     f32x16 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    wgrad_zero<FM * FN>(&acc[0][0]);
 
     if (kt_begin < kt_end) {
         compute_offsets(kt_begin, 0);
@@ -1944,50 +1913,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_bf16_kernel(const erd_
             __syncthreads();
         }
     }
-    float* __restrict__ part = p.part + (int64_t)bz * p.Cout * p.ntaps * p.Cin;
-    if ((p.Cin & 3) == 0) {
-        // partial slab through the (now idle) operand buffers, 64 accumulator rows at a time, written as 16-byte pieces of whole slab
-        // rows instead of 64 four-byte stores per lane (conv_wgrad_row3_x3_kernel does the same)
-        constexpr int SLDW = BN + 4, RPASS = 64, C4 = BN / 4;
-        static_assert(RPASS * SLDW * 4 <= 2 * (BM + BN) * 8 * 16 && FM * 32 == RPASS, "slab staging");
-        float* stage = reinterpret_cast<float*>(smem);
-#pragma unroll
-        for (int ps = 0; ps < BM / RPASS; ++ps) {
-            __syncthreads();
-            if (wm == ps) {
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-#pragma unroll
-                    for (int j = 0; j < FN; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            stage[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * SLDW + (wn * FN + j) * 32 + li] = acc[i][j][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int q = 0; q < RPASS * C4 / NTHREADS; ++q) {
-                const int idx = q * NTHREADS + tid;
-                const int row = idx / C4, c4 = idx - row * C4;
-                const int co = co0 + ps * RPASS + row, ci = ci0 + 4 * c4;
-                if (co < p.Cout && ci < p.Cin)
-                    *reinterpret_cast<float4*>(part + ((int64_t)co * p.ntaps + tap) * p.Cin + ci) =
-                        *reinterpret_cast<const float4*>(stage + row * SLDW + 4 * c4);
-            }
-        }
+    float* __restrict__ part = p.part + (int64_t)wk.slab * p.Cout * p.ntaps * p.Cin;
+    if ((p.Cin & 3) == 0) {      // (always: erd_conv_wgrad refuses every other Cin)
+        // partial slab through the (now idle) operand buffers, 64 accumulator rows at a time (channels in order)
+        wgrad_store_staged<FM, FN, (int)L::OPERAND_BYTES, 0, 0>(reinterpret_cast<float*>(smem), part, acc, p, p.ntaps, tap, co0, ci0, WgradLane{wm, wn, li, h}, tid);
         return;
     }
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-        const int ci = ci0 + (wn * FN + j) * 32 + li;
-        if (ci >= p.Cin) continue;
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = co0 + (wm * FM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (co < p.Cout) part[((int64_t)co * p.ntaps + tap) * p.Cin + ci] = acc[i][j][r];
-            }
-    }
+    // Never reached, and kept: without this direct store behind the branch the compiler schedules the K loop above differently (the
+    // global loads of <true, true> in other slots, one ds_read_b128 moved) and the kernel ran 3 % slower, the bf16 step 1.1 %
+    // (EXPERIMENTS 7o).  The three-limb kernel lost the same tail without such a cost.
+    wgrad_store_direct<1, FM, FN>(part, &acc[0][0], p, p.ntaps, tap, co0, ci0, WgradLane{wm, wn, li, h});
 }
 
 // dW[co][k] (+)= rowscale[co] * sum_s part[s][co][k];  rowdot[co] += sum_k w[co][k] * G[co][k]
@@ -2314,21 +2249,20 @@ extern "C" int erd_conv_igemm(const erd_conv_desc* d, erd_stream_t stream) {
 }
 
 namespace {
-template <int BKW, int MINW>
-int launch_wgrad(const erd_wgrad_desc* d, hipStream_t st) {
-    constexpr int BM = 128, BN = 128;
-    const int nci = (d->Cin + BN - 1) / BN, nco = (d->Cout + BM - 1) / BM;
-    const size_t lds = (size_t)2 * BKW * (BM + BN) * sizeof(float) + 2 * BKW * sizeof(int2);
-    auto kern = conv_wgrad_kernel<BM, BN, BKW, MINW>;
+// One weight-gradient launch: `tiles` (ci tiles x taps | kernel rows x co tiles) workgroups per split and group.  Every kernel
+// instantiation has its own copy of this function, and with it its own once-per-process opt-in to its Lds::BYTES of dynamic LDS.
+template <auto Kern, typename Lds, typename... Extra>
+int launch_wgrad(const char* what, const erd_wgrad_desc* d, int tiles, hipStream_t st, Extra... extra) {
+    constexpr size_t lds = Lds::BYTES;
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_done = true;
     }
-    // XCD-aware work order for the split-K siblings too (same speed, fabric traffic 321 -> 178 MB per launch; ERD_XCD=0: off)
-    hipLaunchKernelGGL(kern, dim3(nci * d->ntaps * nco * d->nsplit), dim3(NTHREADS), lds, st, *d, xcd_order_enabled() ? 1 : 0);
-    return erd::check_launch("conv_wgrad");
+    hipLaunchKernelGGL(Kern, dim3(tiles * d->nsplit * d->ngroups), dim3(NTHREADS), lds, st, *d, extra...);
+    return erd::check_launch(what);
 }
+inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 }  // namespace
 
 #ifdef ERD_IGEMM_TRACE
@@ -2374,89 +2308,54 @@ extern "C" int erd_conv_wgrad(const erd_wgrad_desc* d, erd_stream_t stream) {
     ERD_REQUIRE(npix < (1ll << 31), "wgrad: too many pixels");
     ERD_REQUIRE(d->x_elems > 0 && d->dz_elems > 0 && d->x_elems < (1ll << 29) && d->dz_elems < (1ll << 29),
                 "wgrad: tensors must stay below 2 GiB (32-bit buffer byte offsets)");
-    // K-slices of 16 pixels: half the LDS / staging registers of a 32-pixel slice -> four workgroups per CU hide each
-    // other's staging and barrier phases (measured +10 % over 32-pixel slices at two per CU, tools/bench_conv.py)
     ERD_REQUIRE(d->bf16_multiplicands || !(d->x_bf16 || d->dz_bf16), "wgrad: bf16-stored maps need bf16_multiplicands");
+    const hipStream_t st = (hipStream_t)stream;
     if (d->bf16_multiplicands) {
-        const int nci = (d->Cin + 127) / 128, nco = (d->Cout + 127) / 128;
-        const size_t lds = (size_t)2 * (128 + 128) * 8 * sizeof(float4) + 2 * 64 * sizeof(int2);
-        const dim3 grid(nci * d->ntaps * nco * d->nsplit);
-#define ERD_WG_LAUNCH(XB_, DB_)                                                                                        \
-        do {                                                                                                           \
-            static bool attr_done = false;                                                                             \
-            if (!attr_done) {                                                                                          \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_bf16_kernel<XB_, DB_>),             \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
-                attr_done = true;                                                                                      \
-            }                                                                                                          \
-            hipLaunchKernelGGL((conv_wgrad_bf16_kernel<XB_, DB_>), grid, dim3(NTHREADS), lds, (hipStream_t)stream, *d); \
-        } while (0)
-        if (d->x_bf16 && d->dz_bf16) ERD_WG_LAUNCH(true, true);
-        else if (d->x_bf16) ERD_WG_LAUNCH(true, false);
-        else if (d->dz_bf16) ERD_WG_LAUNCH(false, true);
-        else ERD_WG_LAUNCH(false, false);
-#undef ERD_WG_LAUNCH
-        return erd::check_launch("conv_wgrad_bf16");
+        const int tiles = cdiv(d->Cin, 128) * d->ntaps * cdiv(d->Cout, 128);
+        if (d->x_bf16 && d->dz_bf16) return launch_wgrad<conv_wgrad_bf16_kernel<true, true>, WgradBf16Lds>("conv_wgrad_bf16", d, tiles, st);
+        if (d->x_bf16) return launch_wgrad<conv_wgrad_bf16_kernel<true, false>, WgradBf16Lds>("conv_wgrad_bf16", d, tiles, st);
+        if (d->dz_bf16) return launch_wgrad<conv_wgrad_bf16_kernel<false, true>, WgradBf16Lds>("conv_wgrad_bf16", d, tiles, st);
+        return launch_wgrad<conv_wgrad_bf16_kernel<false, false>, WgradBf16Lds>("conv_wgrad_bf16", d, tiles, st);
     }
     static const int variant = getenv("ERD_WGRAD_VARIANT") ? atoi(getenv("ERD_WGRAD_VARIANT")) : 1;   // tuning aid
     const char* row3_env = getenv("ERD_WGRAD_ROW3");          // read per call: tests flip it in-process
     const int row3 = row3_env ? atoi(row3_env) : 1;
-    if (row3 && d->limbs3 && d->Cin % 4 == 0 && erd_wgrad_row3_slices(d) > 0) {
+    // K-slices of the three-tap kernels (0: not a 3x3 / stride 1 / pad 1 layer), with the XCD-contiguous work order in bit 30
+    // (ERD_WGRAD_XCD=0: dispatch order; same speed, fabric traffic 647 -> 239 MB per launch, PMC)
+    static const int row3_xcd = getenv("ERD_WGRAD_XCD") ? atoi(getenv("ERD_WGRAD_XCD")) : 1;
+    const int row3_slices = row3 ? erd_wgrad_row3_slices(d) : 0;
+    const int row3_arg = row3_slices | (row3_xcd ? (1 << 30) : 0);
+    if (d->limbs3 && row3_slices > 0) {
         // three-limb form: 128 (Cout > 64) or 64 output channels x 64 input channels x 3 taps per workgroup
-        const int nslices = erd_wgrad_row3_slices(d);
-        const int fm = d->Cout > 64 ? 2 : 1;
-        const int nci = (d->Cin + 63) / 64, nco = (d->Cout + fm * 64 - 1) / (fm * 64);
-        const size_t lds = (size_t)2 * 3 * (fm * 64 * 32 + 64 * 48) + 8 * (16 + 20) * sizeof(int);      // (a ring of 8 table slots)
-        void (*kern)(const erd_wgrad_desc, const int) = fm == 2 ? conv_wgrad_row3_x3_kernel<2, 1, true> : conv_wgrad_row3_x3_kernel<1, 1, true>;
-        static bool attr_done3[2] = {false, false};
-        if (!attr_done3[fm - 1]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_done3[fm - 1] = true;
-        }
-        static const int row3_xcd = getenv("ERD_WGRAD_XCD") ? atoi(getenv("ERD_WGRAD_XCD")) : 1;
-        hipLaunchKernelGGL(kern, dim3(nci * 3 * nco * d->nsplit * d->ngroups), dim3(NTHREADS), lds, (hipStream_t)stream, *d,
-                           nslices | (row3_xcd ? (1 << 30) : 0));
-        return erd::check_launch("conv_wgrad_row3_x3");
+        const int tiles = cdiv(d->Cin, 64) * 3;
+        if (d->Cout > 64)
+            return launch_wgrad<conv_wgrad_row3_x3_kernel<2, 1, true>, WgradX3Lds<2, 1, true>>("conv_wgrad_row3_x3", d, tiles * cdiv(d->Cout, 128), st,
+                                                                                              row3_arg);
+        return launch_wgrad<conv_wgrad_row3_x3_kernel<1, 1, true>, WgradX3Lds<1, 1, true>>("conv_wgrad_row3_x3", d, tiles * cdiv(d->Cout, 64), st, row3_arg);
     }
-    if (d->limbs3 && d->Cin % 4 == 0) {
+    if (d->limbs3) {
         // three-limb form of every other layer (1x1, stride 2): one tap, 128 x 128 channels per workgroup, 16-pixel slices of the
         // concatenated pixel axis
-        const int nslices = (int)((npix + 15) / 16);
-        const int nci = (d->Cin + 127) / 128, nco = (d->Cout + 127) / 128;
         for (int l = 0; l < d->nseg; ++l)      // (the kernel steps through the maps row by row)
             ERD_REQUIRE(d->seg[l].N >= 1 && d->seg[l].GH >= 1 && d->seg[l].GW >= 1, "wgrad: empty map %d", l);
-        const size_t lds = (size_t)2 * 3 * (128 * 32 + 128 * 32) + 8 * (16 + 16) * sizeof(int);      // (a ring of 8 table slots)
-        void (*kern)(const erd_wgrad_desc, const int) = conv_wgrad_row3_x3_kernel<2, 2, false>;
-        static bool attr_done1 = false;
-        if (!attr_done1) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_done1 = true;
-        }
-        hipLaunchKernelGGL(kern, dim3(nci * d->ntaps * nco * d->nsplit * d->ngroups), dim3(NTHREADS), lds, (hipStream_t)stream, *d,
-                           nslices | (xcd_order_enabled() ? (1 << 30) : 0));
-        return erd::check_launch("conv_wgrad_x3");
+        const int tiles = cdiv(d->Cin, 128) * d->ntaps * cdiv(d->Cout, 128);
+        return launch_wgrad<conv_wgrad_row3_x3_kernel<2, 2, false>, WgradX3Lds<2, 2, false>>("conv_wgrad_x3", d, tiles, st,
+                                                                                             (int)((npix + 15) / 16) | (xcd_order_enabled() ? (1 << 30) : 0));
     }
-    if (row3 && erd_wgrad_row3_slices(d) > 0) {
-        const int nslices = erd_wgrad_row3_slices(d);
-        const int bme = d->Cout <= 64 ? 64 : (d->Cout <= 96 ? 96 : 128);
-        const int nci = (d->Cin + 127) / 128, nco = (d->Cout + bme - 1) / bme;
-        const size_t lds = (size_t)2 * (16 * 128 + 18 * 128) * sizeof(float) + 2 * (16 + 18) * sizeof(int);
-        void (*kern)(const erd_wgrad_desc, const int) =
-            bme == 64 ? conv_wgrad_row3_kernel<1, 2, 1> : (bme == 96 ? conv_wgrad_row3_kernel<1, 3, 1> : conv_wgrad_row3_kernel<2, 2, 2>);
-        static bool attr_done[3] = {false, false, false};
-        const int vi = bme == 64 ? 0 : (bme == 96 ? 1 : 2);
-        if (!attr_done[vi]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_done[vi] = true;
-        }
-        // XCD-aware work order (ERD_WGRAD_XCD=0: dispatch order): same speed, fabric traffic 647 -> 239 MB per launch (PMC)
-        static const int row3_xcd = getenv("ERD_WGRAD_XCD") ? atoi(getenv("ERD_WGRAD_XCD")) : 1;
-        hipLaunchKernelGGL(kern, dim3(nci * 3 * nco * d->nsplit), dim3(NTHREADS), lds, (hipStream_t)stream, *d,
-                           nslices | (row3_xcd ? (1 << 30) : 0));
-        return erd::check_launch("conv_wgrad_row3");
+    if (row3_slices > 0) {
+        // fp32 MFMA, three taps per workgroup: 64, 96 or 128 output channels x 128 input channels
+        const int tiles = cdiv(d->Cin, 128) * 3;
+        using Lds = WgradF32Lds<128, 128, 16, 18>;
+        if (d->Cout <= 64) return launch_wgrad<conv_wgrad_row3_kernel<1, 2, 1>, Lds>("conv_wgrad_row3", d, tiles * cdiv(d->Cout, 64), st, row3_arg);
+        if (d->Cout <= 96) return launch_wgrad<conv_wgrad_row3_kernel<1, 3, 1>, Lds>("conv_wgrad_row3", d, tiles * cdiv(d->Cout, 96), st, row3_arg);
+        return launch_wgrad<conv_wgrad_row3_kernel<2, 2, 2>, Lds>("conv_wgrad_row3", d, tiles * cdiv(d->Cout, 128), st, row3_arg);
     }
-    if (variant == 0) return launch_wgrad<32, 2>(d, (hipStream_t)stream);
-    return launch_wgrad<16, 4>(d, (hipStream_t)stream);
+    // fp32 MFMA, one tap per workgroup.  K-slices of 16 pixels: half the LDS / staging registers of a 32-pixel slice -> four workgroups per CU
+    // hide each other's staging and barrier phases (measured +10 % over 32-pixel slices at two per CU, tools/bench_conv.py).  XCD-contiguous
+    // order for the split-K siblings too (same speed, fabric traffic 321 -> 178 MB per launch; ERD_XCD=0: off)
+    const int tiles = cdiv(d->Cin, 128) * d->ntaps * cdiv(d->Cout, 128), xcd = xcd_order_enabled() ? 1 : 0;
+    if (variant == 0) return launch_wgrad<conv_wgrad_kernel<128, 128, 32, 2>, WgradF32Lds<128, 128, 32>>("conv_wgrad", d, tiles, st, xcd);
+    return launch_wgrad<conv_wgrad_kernel<128, 128, 16, 4>, WgradF32Lds<128, 128, 16>>("conv_wgrad", d, tiles, st, xcd);
 }
 
 extern "C" int erd_wgrad_reduce(const float* part, int nsplit, int Cout, int K, const float* w,

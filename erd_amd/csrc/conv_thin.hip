@@ -83,10 +83,7 @@ __global__ __launch_bounds__(256, 2) void conv_thin_x3_kernel(const erd_conv_des
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, h = lane >> 5;
     const int G = gridDim.x;
     int wg = blockIdx.x;
-    if (xcd_order) {       // workgroup b runs on XCD b % 8: a contiguous chunk of the work list per XCD (conv_igemm_kernel)
-        const int q = G >> 3, r = G & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    if (xcd_order) wg = erd::xcd_contiguous(blockIdx.x, G);       // a contiguous chunk of the work list per XCD (conv_igemm_kernel)
     const long long T = (long long)mtiles * nb;
     const long long t_begin = T * wg / G, t_end = T * (wg + 1) / G;
     if (t_begin >= t_end) return;
@@ -367,10 +364,7 @@ __global__ __launch_bounds__(256, (KS <= 8 ? 4 : (KS > 16 || (RES && MSK) ? 2 : 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, h = lane >> 5;
     const int G = gridDim.x;
     int wg = blockIdx.x;
-    if (xcd_order) {
-        const int q = G >> 3, r = G & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    if (xcd_order) wg = erd::xcd_contiguous(blockIdx.x, G);
     const long long T = (long long)mtiles * nb;
     const long long t_begin = T * wg / G, t_end = T * (wg + 1) / G;
     if (t_begin >= t_end) return;

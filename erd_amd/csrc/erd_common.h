@@ -104,6 +104,13 @@ __device__ __forceinline__ T* uniform_ptr(T* p) {
 }
 __device__ __forceinline__ int uniform_int(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// XCD-contiguous work order of a 1-D grid: workgroup b runs on XCD b % 8 and each XCD has its own L2, so XCD x takes the x-th CONTIGUOUS
+// chunk of the work list (the first grid % 8 chunks one item longer) and neighbours in the list share an L2.  Bijective for any grid.
+__device__ __forceinline__ int xcd_contiguous(unsigned block, int grid) {
+    const int q = grid >> 3, r = grid & 7, xcd = block & 7, idx = block >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
 // ---- three-limb split ("f32x3"): an fp32 value as the EXACT sum of three bf16 values, each rounded to nearest even:
 //   hi = rne(x), mid = rne(x - hi), lo = x - hi - mid      (x - hi has <= 16 significant bits, x - hi - mid <= 8: both exact)
 // |mid| <= 2^-8 |x|, |lo| <= 2^-16 |x| (half an ulp of the limb above), and the remainders are SIGN-SYMMETRIC around zero --

@@ -17,14 +17,7 @@ pytestmark = pytest.mark.gpu
 
 import golden_inputs as G
 
-N = 2
-# one tap: output sizes per segment, and the input sizes of the 3x3 / stride-2 / pad-1 form that produce them
-GEOM = {
-    "narrow": dict(out=[(7, 11), (4, 6)], in_s2=[(13, 21), (8, 12)]),                      # every map narrower than 16: per-lane decode
-    "wide": dict(out=[(6, 19), (3, 37), (4, 6)], in_s2=[(11, 37), (5, 73), (8, 12)]),      # row wraps, image and segment crossings in a pass
-}
-CONV = {"1x1": (1, 1, 0), "3x3s2": (3, 2, 1)}
-ROW3_SIZES = [(13, 21), (7, 11), (20, 36)]
+from wgrad_refs import CONV, GEOM, N, ROW3_SIZES, _nsplits      # the shapes and split counts (shared with test_gpu_wgrad_exact.py)
 
 
 def _slices_one_tap(geom):
@@ -33,14 +26,6 @@ def _slices_one_tap(geom):
 
 def _slices_row3():
     return N * sum(h * ((w + 15) // 16) for h, w in ROW3_SIZES)
-
-
-def _nsplits(ns):
-    """1, the first split count that leaves the last split short, the first that leaves exactly one split empty"""
-    per = lambda s: -(-ns // s)
-    short = next(s for s in range(2, ns) if (s - 1) * per(s) < ns < s * per(s))
-    empty = next(s for s in range(2, ns + 2) if (s - 2) * per(s) < ns <= (s - 1) * per(s))
-    return [1, short, empty]
 
 
 def test_the_cases_are_what_they_claim():
