@@ -152,6 +152,74 @@ int xcd_order_enabled() {
     return v;
 }
 
+// Parts of conv_igemm_kernel that are defined once: its LDS layout, a workgroup's unit range, the decode of a GEMM row, and where a
+// workgroup's stream-K slab lies.  The tile decode, the K loops with their loaders, the hand-over and the two epilogues are the kernel's
+// own text: each of them, moved into a function of its own, moved the K loops of other instantiations (EXPERIMENTS 7p).
+// Dynamic LDS of one instantiation, in bytes from its start.  The epilogue's staging re-uses the operand region: [64][BN + 4] floats + [NT]
+// float4 of column-sum scratch, shared by the workgroup (fp32 / bf16), or one [32][BN + 4] block per wave (f32x3); row table and
+// broadcast word follow the region.  f32x3: the operand region is 80 KB at 128 x 128 -- exactly half of the CU's LDS, two workgroups per
+// CU only if nothing else is allocated.  The row table therefore lives INSIDE the region: at its start while a tile is set up (before
+// the first operand slice is stored) and behind the staging blocks once the K loop is over (recomputed: 128 threads, two divisions
+// each), with the broadcast word of the stream-K hand-over and the column-sum scratch [4 waves][BN / 4] float4 next to it.
+template <int BM, int BN, int NT, int BKT, bool X3>
+struct IgemmLds {
+    static constexpr int CH = BKT / 4;               // 16-B chunks per K-slice row (8 for BK=32, 4 for BK=16)
+    static constexpr int CHB = X3 ? 4 : CH;          // ... of ONE weight plane (f32x3: 8 bf16 per chunk)
+    static constexpr int NPL = X3 ? 3 : 1;           // weight planes
+    static constexpr int SLD = BN + 4;               // floats per staged row
+    static constexpr int B_OFF = 2 * BM * CH * 16;
+    static constexpr int OPER_BYTES = B_OFF + 2 * NPL * BN * CHB * 16;
+    static constexpr int STAGE_BYTES = 64 * SLD * 4 + NT * 16;
+    static constexpr int WSTAGE_BYTES = 32 * SLD * 4;
+    static constexpr int REGION = OPER_BYTES > STAGE_BYTES ? OPER_BYTES : STAGE_BYTES;
+    static constexpr int ROWS_OFF = X3 ? 0 : REGION;                                              // RowInfo [BM] while a tile is set up
+    static constexpr int ROWS_EPI_OFF = X3 ? (4 * WSTAGE_BYTES + 255) / 256 * 256 : REGION;       // ... and for the epilogue
+    static constexpr int BCAST_OFF = ROWS_EPI_OFF + BM * (int)sizeof(RowInfo);                    // int [4]
+    static constexpr int RED_OFF = X3 ? BCAST_OFF + 64 : 64 * SLD * 4;                            // column-sum scratch
+    static constexpr int RED_BYTES = X3 ? 4 * (BN / 4) * 16 : NT * 16;
+    static constexpr int BYTES = X3 ? OPER_BYTES : REGION + BM * (int)sizeof(RowInfo) + 16;
+    static_assert(RED_OFF + RED_BYTES <= (X3 ? OPER_BYTES : REGION), "column-sum scratch does not fit behind the staged rows");
+};
+
+// The first unit of position b of the work order (a workgroup's units end where the next position's begin); whole_tiles: of its first tile.
+__device__ __forceinline__ long long sk_first_unit(long long U, int b, int G) { return (U * b) / G; }
+__device__ __forceinline__ long long igemm_first_unit(const SkWs& ws, int total_tiles, int nkt, int b, int G) {
+    return ws.whole_tiles ? ((long long)total_tiles * b / G) * nkt : sk_first_unit((long long)total_tiles * nkt, b, G);
+}
+
+// GEMM row m of a segment: image, top-left input position and output pixel (rows past the end read nothing and store nothing)
+__device__ __forceinline__ RowInfo igemm_row(const erd_conv_desc& p, const erd_conv_seg& sg, int m, int oy, int ox) {
+    const int GHW = sg.GH * sg.GW;
+    RowInfo ri{0, -(1 << 28), -(1 << 28), -1};
+    if (m < sg.N * GHW) {
+        const int n = m / GHW;
+        const int rem = m - n * GHW;
+        const int a = rem / sg.GW;
+        const int b = rem - a * sg.GW;
+        ri.in_off = (int)(n * sg.in_nstride);
+        ri.ih0 = a * p.in_stride;
+        ri.iw0 = b * p.in_stride;
+        ri.out_off = (int)(n * sg.out_nstride) + ((a * p.out_stride + oy) * sg.OW + (b * p.out_stride + ox)) * p.Cout;
+    }
+    return ri;
+}
+
+template <int NACC>
+__device__ __forceinline__ void zero_acc(f32x16* acc) {
+#pragma unroll
+    for (int i = 0; i < NACC; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+}
+
+// Stream-K slabs.  Workgroup b's partial accumulators go to slab 2 b + slot: slot 0 for the tile its unit range starts in, 1 for the tile
+// it ends in.  float4 q = (fragment, register quad) of lane tid lies at [q][tid]: 16-B stores / loads, coalesced.
+__device__ __forceinline__ int sk_slot(int tt, long long first_unit, int nkt) { return tt == (int)(first_unit / nkt) ? 0 : 1; }
+template <int BM, int BN>
+__device__ __forceinline__ unsigned sk_slab_off(int b, int slot, int tid) {
+    return (unsigned)((size_t)(2 * b + slot) * (BM * BN) * 4) + (unsigned)tid * 16u;
+}
+
 // BF = true: the same kernel on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16): a 16-B LDS chunk holds 8 bf16
 // k-values instead of 4 floats (a K-slice is CH*8 values), activations are read as fp32 (two 16-B loads per chunk)
 // and rounded to bf16 on their way into LDS, weights come pre-rounded (erd_conv_desc::w_bf16); accumulation, the
@@ -189,28 +257,16 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
     static_assert(!GL || X3, "LDS-DMA staging: the three-limb kernel (both operands are stored in LDS exactly as they lie in memory)");
     constexpr unsigned ABYTES = AB ? 2u : 4u;   // bytes per stored input value
     constexpr int CHB = X3 ? 4 : CH;            // 16-B chunks per K-slice row of ONE weight plane (f32x3: 8 bf16 per chunk)
-    constexpr int NPL = X3 ? 3 : 1;             // weight planes in LDS
     constexpr int RPPB = NT / CHB;        // weight rows staged per pass
     constexpr int BJX = BN / RPPB;              // 16-B loads per thread and plane for B (f32x3)
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    using Lds = IgemmLds<BM, BN, NT, BKT, X3>;
     float4* As = reinterpret_cast<float4*>(smem);                 // [2][BM*CH]
-    float4* Bs = As + 2 * BM * CH;                                 // [2][BN*CH]   (f32x3: [2][3 planes][BN*4])
-    constexpr int OPER_BYTES = 2 * (BM * CH + NPL * BN * CHB) * 16;
-    constexpr int STAGE_BYTES = 64 * (BN + 4) * 4 + NT * 16;  // epilogue staging (+ column-sum scratch) re-uses the operand region
-    constexpr int REGION = OPER_BYTES > STAGE_BYTES ? OPER_BYTES : STAGE_BYTES;
-    // f32x3: the operand region is 80 KB at 128 x 128 -- exactly half of the CU's LDS, two workgroups per CU only if nothing
-    // else is allocated.  The row table therefore lives INSIDE the region: at its start while a tile is set up (before the
-    // first operand slice is stored) and behind the epilogue's staging area once the K loop is over (recomputed: 128 threads,
-    // two divisions each); the broadcast word of the stream-K fix-up sits next to it.
-    // (f32x3: the epilogue stages each wave's 32 rows in its own block: 4 x 32 x (BN + 4) floats)
-    constexpr int WSTAGE_BYTES = 32 * (BN + 4) * 4;
-    constexpr int ROWS_EPI_OFF = X3 ? ((4 * WSTAGE_BYTES + 255) / 256 * 256) : REGION;
-    static_assert(!X3 || ROWS_EPI_OFF + BM * (int)sizeof(RowInfo) + 64 + 4 * (BN / 4) * 16 <= OPER_BYTES,
-                  "f32x3: row table + column-sum scratch do not fit behind the staging blocks");
-    RowInfo* rows = reinterpret_cast<RowInfo*>(smem + (X3 ? 0 : REGION));     // [BM]
-    RowInfo* rows_epi = reinterpret_cast<RowInfo*>(smem + ROWS_EPI_OFF);
-    int* bcast = reinterpret_cast<int*>(reinterpret_cast<RowInfo*>(smem + ROWS_EPI_OFF) + BM);                // [4]
+    float4* Bs = reinterpret_cast<float4*>(smem + Lds::B_OFF);    // [2][BN*CH]   (f32x3: [2][3 planes][BN*4])
+    RowInfo* rows = reinterpret_cast<RowInfo*>(smem + Lds::ROWS_OFF);     // [BM]
+    RowInfo* rows_epi = reinterpret_cast<RowInfo*>(smem + Lds::ROWS_EPI_OFF);
+    int* bcast = reinterpret_cast<int*>(smem + Lds::BCAST_OFF);                // [4]
 
     const int tid = threadIdx.x;
     const int ntn = (p.Cout + BN - 1) / BN;
@@ -226,8 +282,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
     // hit the same L2 instead of being fetched through the fabric by up to 8 of them.  Bijective for any G.
     int wg = blockIdx.x;
     if (ws.xcd_order) wg = erd::xcd_contiguous(blockIdx.x, G);
-    const long long u_begin = ws.whole_tiles ? ((long long)total_tiles * wg / G) * nkt : (U * wg) / G;
-    const long long u_end = ws.whole_tiles ? ((long long)total_tiles * (wg + 1) / G) * nkt : (U * (wg + 1)) / G;
+    const long long u_begin = igemm_first_unit(ws, total_tiles, nkt, wg, G), u_end = igemm_first_unit(ws, total_tiles, nkt, wg + 1, G);
 
     const int chunk = tid % CH;
     const int r0 = tid / CH;
@@ -278,29 +333,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
 
         __syncthreads();   // previous tile's epilogue / fragment reads are done with LDS
         auto fill_rows = [&](RowInfo* dst) {
-            if (tid < BM) {
-                const int GHW = sg.GH * sg.GW;
-                const int M = sg.N * GHW;
-                const int m = mt * BM + tid;
-                RowInfo ri;
-                if (m < M) {
-                    const int n = m / GHW;
-                    const int rem = m - n * GHW;
-                    const int a = rem / sg.GW;
-                    const int b = rem - a * sg.GW;
-                    ri.in_off = (int)(n * sg.in_nstride);
-                    ri.ih0 = a * p.in_stride;
-                    ri.iw0 = b * p.in_stride;
-                    ri.out_off = (int)(n * sg.out_nstride) +
-                                 ((a * p.out_stride + oy_s) * sg.OW + (b * p.out_stride + ox_s)) * p.Cout;
-                } else {
-                    ri.in_off = 0;
-                    ri.ih0 = -(1 << 28);
-                    ri.iw0 = -(1 << 28);
-                    ri.out_off = -1;
-                }
-                dst[tid] = ri;
-            }
+            if (tid < BM) dst[tid] = igemm_row(p, sg, mt * BM + tid, oy_s, ox_s);
         };
         if constexpr (!GL) {
             fill_rows(rows);
@@ -310,39 +343,23 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
         // per-row byte offset of tap (0,0) and a validity bit per tap: the K loop then needs one add + one select
         // per 16-B load, and zero padding comes from the buffer's out-of-range rule (no branches, no zero fill)
         unsigned a_base[AJ], a_mask[AJ];
-        // (spelled once, expanded at one of two places: a lambda here changes the code of the instantiations that do not move it)
-#define ERD_DECODE_ROWS                                                                                                                            \
-        _Pragma("unroll")                                                                                                                          \
-        for (int j = 0; j < AJ; ++j) {                                                                                                             \
-            RowInfo ri;                                                                                                                            \
-            if constexpr (GL) {      /* no table, no barriers: a thread decodes its own AJ rows (the operand region is filled by DMA) */   \
-                const int GHW = sg.GH * sg.GW;                                                                                                     \
-                const int m = mt * BM + r0 + RPP * j;                                                                                              \
-                if (m < sg.N * GHW) {                                                                                                              \
-                    const int n = m / GHW;                                                                                                         \
-                    const int rem = m - n * GHW;                                                                                                   \
-                    const int a = rem / sg.GW;                                                                                                     \
-                    ri.in_off = (int)(n * sg.in_nstride);                                                                                          \
-                    ri.ih0 = a * p.in_stride;                                                                                                      \
-                    ri.iw0 = (rem - a * sg.GW) * p.in_stride;                                                                                      \
-                } else {                                                                                                                           \
-                    ri.in_off = 0;                                                                                                                 \
-                    ri.ih0 = -(1 << 28);                                                                                                           \
-                    ri.iw0 = -(1 << 28);                                                                                                           \
-                }                                                                                                                                  \
-            } else {                                                                                                                               \
-                ri = rows[r0 + RPP * j];                                                                                                           \
-            }                                                                                                                                      \
-            a_base[j] = (unsigned)(ri.in_off + (ri.ih0 * IW + ri.iw0) * Cin + chunk_l * KPC) * ABYTES;                                             \
-            unsigned m = 0;                                                                                                                        \
-            for (int t = 0; t < nt_s; ++t) {                                                                                                       \
-                const int ih = ri.ih0 + p.dy[tap_lo + t], iw = ri.iw0 + p.dx[tap_lo + t];                                                          \
-                m |= ((unsigned)ih < (unsigned)IH && (unsigned)iw < (unsigned)IW) ? (1u << t) : 0u;                                                \
-            }                                                                                                                                      \
-            a_mask[j] = m;                                                                                                                         \
-        }
+        // (called at one of two places.  As a lambda it changes the register numbering of every instantiation and no K loop: EXPERIMENTS 7p)
+        auto decode_rows = [&]() {
+#pragma unroll
+            for (int j = 0; j < AJ; ++j) {
+                // GL: no table, no barriers: a thread decodes its own AJ rows (the operand region is filled by DMA)
+                const RowInfo ri = GL ? igemm_row(p, sg, mt * BM + r0 + RPP * j, oy_s, ox_s) : rows[r0 + RPP * j];
+                a_base[j] = (unsigned)(ri.in_off + (ri.ih0 * IW + ri.iw0) * Cin + chunk_l * KPC) * ABYTES;
+                unsigned m = 0;
+                for (int t = 0; t < nt_s; ++t) {
+                    const int ih = ri.ih0 + p.dy[tap_lo + t], iw = ri.iw0 + p.dx[tap_lo + t];
+                    m |= ((unsigned)ih < (unsigned)IH && (unsigned)iw < (unsigned)IW) ? (1u << t) : 0u;
+                }
+                a_mask[j] = m;
+            }
+        };
         // GL: the tile's first weight requests depend on nothing in the decode (two integer divisions per row): they go out in front of it
-        if constexpr (!GL) { ERD_DECODE_ROWS }
+        if constexpr (!GL) decode_rows();
         const int n0 = nt * BN;
         unsigned b_base[X3 ? 1 : BJ];
         unsigned bx_base[X3 ? BJX : 1];            // f32x3: byte offset of (cout row, 8-value chunk) inside ONE bf16 weight plane
@@ -408,7 +425,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
         };
         auto glds_b = [&](int j, const int buf, auto fresh, auto&... tie) {      // j = plane * BJX + row pass
             const int pl = j / BJX, jj = j - pl * BJX;
-            glds16_sel(fresh, rw_w, lds0 + (unsigned)((2 * BM * CH + (buf * 3 + pl) * BN * CHB + (RPPB * jj + 16 * wave_s) * CHB) * 16),
+            glds16_sel(fresh, rw_w, lds0 + (unsigned)(Lds::B_OFF + ((buf * 3 + pl) * BN * CHB + (RPPB * jj + 16 * wave_s) * CHB) * 16),
                    cokb ? bx_base[X3 ? jj : 0] + (unsigned)bdelta + (unsigned)pl * plane_b : OOB, tie...);
         };
         auto load_a = [&](int j, const int set) {
@@ -471,11 +488,10 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
             glds_b(0, 0, bool_c<true>{});
 #pragma unroll
             for (int j = 1; j < NBL; ++j) glds_b(j, 0, bool_c<false>{});
-            { ERD_DECODE_ROWS }      // (under the weight requests' latency)
+            decode_rows();      // (under the weight requests' latency)
 #pragma unroll
             for (int j = 0; j < AJ; ++j) glds_a(j, 0);
             glds_wait_all();
-#undef ERD_DECODE_ROWS
         } else {
 #pragma unroll
         for (int j = 0; j < AJ; ++j) load_a(j, 0);
@@ -748,15 +764,13 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
             const int first_b = (int)(((t0 + 1) * G - 1) / U);
             const int last_b = (int)(((t0 + nkt) * G - 1) / U);
             const int ncontrib = last_b - first_b + 1;
-            const int my_slot = (tt == (int)(u_begin / nkt)) ? 0 : 1;
-            // slab layout: float4 q = (fragment, register quad) of lane tid at [q][tid]: 16-B stores/loads, coalesced
             // Slabs travel with sc1 (write-through) stores and sc1 loads: visible across the XCDs' L2s without the
             // agent-scope release / acquire fences, whose `buffer_wbl2 sc1` writes back EVERY dirty line of the XCD's L2
             // (the output rows other workgroups have just stored) -- measured 27k cycles per workgroup in this hand-over
             // on the 264-tile 1x1 layers, a seventh of the kernel (cdna_hip_programming Guideline 16, sc1 form).
             const __amdgpu_buffer_rsrc_t rs_slab = __builtin_amdgcn_make_buffer_rsrc(
                 ws.slabs, 0, (int)std::min<size_t>((size_t)2 * G * BM * BN * 4, 0x7fffffffu), 0x00020000);
-            const unsigned slab_off = (unsigned)((size_t)(2 * wg + my_slot) * (BM * BN) * 4) + (unsigned)tid * 16u;
+            const unsigned slab_off = sk_slab_off<BM, BN>(wg, sk_slot(tt, u_begin, nkt), tid);
 #pragma unroll
             for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -777,19 +791,11 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
             // accumulators and adds the other slab.  Three or more: re-sum every slab in K order from zero so the
             // result does not depend on who arrived last.
             const bool pair = ncontrib == 2;
-            if (!pair) {
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-#pragma unroll
-                    for (int j = 0; j < FN; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-            }
+            if (!pair) zero_acc<FM * FN>(&acc[0][0]);
             for (int c = 0; c < ncontrib; ++c) {
                 const int bb = first_b + c;
                 if (pair && bb == wg) continue;
-                const int bfirst_tile = (int)(((U * bb) / G) / nkt);
-                const unsigned so = (unsigned)((size_t)(2 * bb + (tt == bfirst_tile ? 0 : 1)) * (BM * BN) * 4) + (unsigned)tid * 16u;
+                const unsigned so = sk_slab_off<BM, BN>(bb, sk_slot(tt, sk_first_unit(U, bb, G), nkt), tid);
 #pragma unroll
                 for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -828,7 +834,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
             // four sequential passes with two barriers each: 14 k of a tile's 56 k cycles on the K = 256 layers).
             {   // (Cout % 4 == 0: erd_conv_igemm sends other launches to the fp32 kernel)
                 __syncthreads();                                // the row table behind the staging blocks is complete
-                float* wst = reinterpret_cast<float*>(smem + wave * WSTAGE_BYTES);
+                float* wst = reinterpret_cast<float*>(smem + wave * Lds::WSTAGE_BYTES);
                 constexpr int RPW = 64 / C4N, NIT = 32 / RPW;   // rows per wave-instruction, instructions per block
                 const int c4 = lane % C4N, rsub = lane / C4N;
                 const int co = n0 + c4 * 4;
@@ -920,7 +926,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
                         csum.x += __shfl_xor(csum.x, o, 64); csum.y += __shfl_xor(csum.y, o, 64);
                         csum.z += __shfl_xor(csum.z, o, 64); csum.w += __shfl_xor(csum.w, o, 64);
                     }
-                    float4* red = reinterpret_cast<float4*>(smem + ROWS_EPI_OFF + BM * sizeof(RowInfo) + 64);      // [4][C4N], behind table + broadcast word
+                    float4* red = reinterpret_cast<float4*>(smem + Lds::RED_OFF);      // [4][C4N], behind table + broadcast word
                     if (lane < C4N) red[wave * C4N + lane] = cvalid ? csum : make_float4(0.f, 0.f, 0.f, 0.f);
                     __syncthreads();
                     if (tid < C4N && n0 + tid * 4 < p.Cout) {
@@ -1014,7 +1020,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, MINW) void conv_igemm_kerne
             }
             if (p.colsum) {     // per-channel sum of what was stored (d beta of the upstream BN): LDS-combine the row
                                 // lanes, then one atomic per channel per half tile
-                float4* red = reinterpret_cast<float4*>(stage + 64 * SLD);      // [RPS][C4N], behind the staged rows
+                float4* red = reinterpret_cast<float4*>(smem + Lds::RED_OFF);      // [RPS][C4N], behind the staged rows
                 __syncthreads();
                 red[tid] = (co < p.Cout) ? csum_keep : make_float4(0.f, 0.f, 0.f, 0.f);
                 __syncthreads();
@@ -1128,14 +1134,6 @@ struct WgradRsrc { __amdgpu_buffer_rsrc_t dz, x; };
 __device__ __forceinline__ WgradRsrc wgrad_rsrc(const erd_wgrad_desc& p, const void* dz, const void* x, int dz_bytes = 4, int x_bytes = 4) {
     return {__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(dz), 0, (int)(p.dz_elems * dz_bytes), 0x00020000),
             __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(x), 0, (int)(p.x_elems * x_bytes), 0x00020000)};
-}
-
-template <int NACC>
-__device__ __forceinline__ void wgrad_zero(f32x16* acc) {
-#pragma unroll
-    for (int i = 0; i < NACC; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
 }
 
 // Where a wave's accumulators go: wave (wm, wn) owns FM x FN 32x32 blocks, lane (li, h) of block (i, j) holds column (wn * FN + j) * 32 + li
@@ -1300,7 +1298,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void conv_wgrad_kernel(const erd_wg
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, h = lane >> 5;
     f32x16 acc[FM][FN];
-    wgrad_zero<FM * FN>(&acc[0][0]);
+    zero_acc<FM * FN>(&acc[0][0]);
 
     if (kt_begin < kt_end) {
         compute_offsets(kt_begin, 0);
@@ -1437,7 +1435,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_row3_kernel(const erd_
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int li = lane & 31, h = lane >> 5;
     f32x16 acc[3][FM][FN];
-    wgrad_zero<3 * FM * FN>(&acc[0][0][0]);
+    zero_acc<3 * FM * FN>(&acc[0][0][0]);
 
     if (kt_begin < kt_end) {
         compute_offsets(kt_begin, 0);
@@ -1685,7 +1683,7 @@ __global__ __launch_bounds__(NTHREADS, ERD_W3X3_MINW) void conv_wgrad_row3_x3_ke
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, h = lane >> 5;
     f32x16 acc[NT][FM][FN];
-    wgrad_zero<NT * FM * FN>(&acc[0][0][0]);
+    zero_acc<NT * FM * FN>(&acc[0][0][0]);
 
     if (kt_begin < kt_end) {
         if (wave_u == 0) table_pass(kt_begin);
@@ -1872,7 +1870,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_bf16_kernel(const erd_
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, h = lane >> 5;
     f32x16 acc[FM][FN];
-    wgrad_zero<FM * FN>(&acc[0][0]);
+    zero_acc<FM * FN>(&acc[0][0]);
 
     if (kt_begin < kt_end) {
         compute_offsets(kt_begin, 0);
@@ -2061,36 +2059,17 @@ int num_cus() {
     return n;
 }
 
-template <int BM, int BN, int WM, int WN, int BKT, int MINW, bool BF = false, bool ST = false, bool AB = false, bool OB = false,
-          bool X3 = false, bool RES = false, bool MSK = false, bool GL = false>
-int launch_igemm(const erd_conv_desc* d, hipStream_t st) {
-    constexpr int NT = WM * WN * 64;
-    constexpr int BK = (BKT / 4) * (BF ? 8 : 4);
-    int tiles = 0;
-    for (int s = 0; s < d->nseg; ++s) {
-        const int64_t M = (int64_t)d->seg[s].N * d->seg[s].GH * d->seg[s].GW;
-        tiles += (int)((M + BM - 1) / BM);
-    }
-    const int ntn = (d->Cout + BN - 1) / BN;
-    tiles *= ntn;
-    if (tiles == 0) return 0;
-    const int nkt = d->ntaps * ((d->Cin + BK - 1) / BK);
-    const size_t oper = X3 ? (size_t)2 * (BM * 8 + 3 * BN * 4) * sizeof(float4) : (size_t)2 * (BM + BN) * (BKT / 4) * sizeof(float4);
-    const size_t stage = (size_t)64 * (BN + 4) * 4 + NT * 16;
-    // (f32x3: the row table and the fix-up's broadcast word live inside the operand region -- see the kernel)
-    static const size_t lds_pad = getenv("ERD_IG_LDS_PAD") ? (size_t)atoi(getenv("ERD_IG_LDS_PAD")) : 0;   // occupancy experiments
-    const size_t lds = (X3 ? oper : (oper > stage ? oper : stage) + BM * sizeof(RowInfo) + 16) + lds_pad;
-    auto kern = conv_igemm_kernel<BM, BN, WM, WN, BKT, MINW, BF, ST, AB, OB, X3, RES, MSK, GL>;
-    static bool attr_done = false;  // idempotent, value never changes: benign race
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
-    }
-    // persistent stream-K grid when a workspace is supplied and tile-granular dispatch would leave a
-    // ragged last round; otherwise one workgroup per tile.
+// What erd_conv_igemm counts once per launch, before it picks an instantiation: the M-tiles of 128 rows of all segments (every
+// instantiation has 128-row tiles), and whether a segment has a tap set of its own (merged parity classes of a stride-2 input gradient)
+struct IgemmShape { int64_t mtiles; bool seg_taps; };
+
+// The grid of one launch and its stream-K workspace: one workgroup per tile, or a PERSISTENT grid of G workgroups over the units (tiles x
+// K-slices) when a workspace is supplied and tile-granular dispatch would leave a ragged last round.  Depends on the instantiation
+// through BKT (16-B chunks x 4 per K-slice row), MINW (workgroups per CU) and BF (bf16 matrix cores) only.  Returns G, fills `ws`.
+int igemm_plan(const erd_conv_desc* d, const IgemmShape& sh, int tiles, int nkt, int BKT, int MINW, bool BF, SkWs& ws) {
     const int slots = MINW * erd::usable_cus(num_cus());
     int G = tiles;
-    SkWs ws{nullptr, nullptr, xcd_order_enabled(), 0};
+    ws = SkWs{nullptr, nullptr, xcd_order_enabled(), 0};
     // workspace layout (fixed, independent of this launch's tile count): [slabs: 2*slots*128*128 floats][tickets]
     const size_t slab_bytes = (size_t)2 * 4 * num_cus() * 128 * 128 * sizeof(float);
     const size_t need = slab_bytes + (size_t)tiles * sizeof(int);
@@ -2105,11 +2084,11 @@ int launch_igemm(const erd_conv_desc* d, hipStream_t st) {
     static const int min_slices = getenv("ERD_SK_MIN_SLICES") ? atoi(getenv("ERD_SK_MIN_SLICES")) : 8;
     const int64_t units = (int64_t)tiles * nkt;
     const bool tiny = units < slots && min_slices > 0 && nkt >= 2 * min_slices && !BF;
-    bool seg_taps = false;           // per-segment tap sets: tiles have different K lengths -> whole tiles only,
-    for (int s = 0; s < d->nseg; ++s) seg_taps |= d->seg[s].ntaps > 0;     // dealt round-robin over the XCDs (a contiguous
-    if (seg_taps) ws.xcd_order = 0;  // chunk per XCD would hand one XCD all the 4-tap tiles and another all the 1-tap ones)
+    // per-segment tap sets: tiles have different K lengths -> whole tiles only, dealt round-robin over the XCDs (a contiguous
+    // chunk per XCD would hand one XCD all the 4-tap tiles and another all the 1-tap ones)
+    if (sh.seg_taps) ws.xcd_order = 0;
     static const int sk_min_k = getenv("ERD_SK_MIN_K") ? atoi(getenv("ERD_SK_MIN_K")) : 512;
-    if (d->sk_ws && d->sk_ws_bytes >= need && ragged && sk_pays && !seg_taps && nkt * BKT >= sk_min_k && (units >= slots || tiny)) {
+    if (d->sk_ws && d->sk_ws_bytes >= need && ragged && sk_pays && !sh.seg_taps && nkt * BKT >= sk_min_k && (units >= slots || tiny)) {
         G = (int)std::min<int64_t>(slots, min_slices > 0 ? std::max<int64_t>(tiles, units / min_slices) : slots);
         ws.slabs = reinterpret_cast<float*>(d->sk_ws);
         ws.cnt = reinterpret_cast<int*>(reinterpret_cast<char*>(d->sk_ws) + slab_bytes);
@@ -2118,10 +2097,32 @@ int launch_igemm(const erd_conv_desc* d, hipStream_t st) {
     }
     // persistent whole tiles (experiment, ERD_PT=1): launches that stay tile-parallel and have more tiles than resident slots
     static const int pt = getenv("ERD_PT") ? atoi(getenv("ERD_PT")) : 0;
-    if (pt && !ws.slabs && !seg_taps && tiles > slots) {
+    if (pt && !ws.slabs && !sh.seg_taps && tiles > slots) {
         G = slots;
         ws.whole_tiles = 1;
     }
+    return G;
+}
+// One instantiation: its kernel, its once-per-process opt-in to its dynamic LDS, the launch.
+template <int BM, int BN, int WM, int WN, int BKT, int MINW, bool BF = false, bool ST = false, bool AB = false, bool OB = false,
+          bool X3 = false, bool RES = false, bool MSK = false, bool GL = false>
+int launch_igemm(const erd_conv_desc* d, hipStream_t st, const IgemmShape& sh) {
+    static_assert(BM == 128, "IgemmShape counts M-tiles of 128 rows");
+    constexpr int NT = WM * WN * 64;
+    constexpr int BK = (BKT / 4) * (BF ? 8 : 4);
+    const int tiles = (int)sh.mtiles * ((d->Cout + BN - 1) / BN);
+    if (tiles == 0) return 0;
+    const int nkt = d->ntaps * ((d->Cin + BK - 1) / BK);
+    static const size_t lds_pad = getenv("ERD_IG_LDS_PAD") ? (size_t)atoi(getenv("ERD_IG_LDS_PAD")) : 0;   // occupancy experiments
+    const size_t lds = IgemmLds<BM, BN, NT, BKT, X3>::BYTES + lds_pad;
+    auto kern = conv_igemm_kernel<BM, BN, WM, WN, BKT, MINW, BF, ST, AB, OB, X3, RES, MSK, GL>;
+    static bool attr_done = false;  // idempotent, value never changes: benign race
+    if (!attr_done) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_done = true;
+    }
+    SkWs ws;
+    const int G = igemm_plan(d, sh, tiles, nkt, BKT, MINW, BF, ws);
     hipLaunchKernelGGL(kern, dim3(G), dim3(NT), lds, st, *d, tiles, ws);
     return erd::check_launch("conv_igemm");
 }
@@ -2154,17 +2155,20 @@ extern "C" int erd_conv_igemm(const erd_conv_desc* d, erd_stream_t stream) {
     // kernel; short ones (1x1 convs on <=256 channels) are prologue/epilogue-latency bound and want many small
     // co-resident workgroups (BK=16, half the LDS and staging registers -> 4 workgroups per CU).
     static const int variant = getenv("ERD_IGEMM_VARIANT") ? atoi(getenv("ERD_IGEMM_VARIANT")) : 0;   // tuning aid
-    bool seg_taps_any = false;
-    for (int s = 0; s < d->nseg; ++s) seg_taps_any |= d->seg[s].ntaps > 0;
+    IgemmShape sh{0, false};
+    for (int s = 0; s < d->nseg; ++s) {
+        sh.mtiles += ((int64_t)d->seg[s].N * d->seg[s].GH * d->seg[s].GW + 127) / 128;
+        sh.seg_taps |= d->seg[s].ntaps > 0;
+    }
     if (d->w_bf16 && erd::conv_thin_bf16_ok(d)) return erd::conv_thin_bf16(d, st);      // thin 1x1 layers on bf16 maps: activations stationary
     if (d->w_bf16) {    // bf16 matrix cores: the loaders, not the MFMAs, set the pace -> the plain 2-workgroup variant
         // storage of the maps (in_bf16 / out_bf16) picks the instantiation: 0 = fp32 in HBM, 1 = bf16 in HBM
 #define ERD_BF_LAUNCH(AB_, OB_)                                                                       \
         do {                                                                                          \
-            if (seg_taps_any) return launch_igemm<128, 128, 2, 2, 32, 2, true, true, AB_, OB_>(d, st);  \
-            if (variant == 2) return launch_igemm<128, 128, 2, 2, 16, 4, true, false, AB_, OB_>(d, st); \
-            if (d->Cout <= 64) return launch_igemm<128, 64, 2, 2, 32, 2, true, false, AB_, OB_>(d, st); \
-            return launch_igemm<128, 128, 2, 2, 32, 2, true, false, AB_, OB_>(d, st);                   \
+            if (sh.seg_taps) return launch_igemm<128, 128, 2, 2, 32, 2, true, true, AB_, OB_>(d, st, sh);  \
+            if (variant == 2) return launch_igemm<128, 128, 2, 2, 16, 4, true, false, AB_, OB_>(d, st, sh); \
+            if (d->Cout <= 64) return launch_igemm<128, 64, 2, 2, 32, 2, true, false, AB_, OB_>(d, st, sh); \
+            return launch_igemm<128, 128, 2, 2, 32, 2, true, false, AB_, OB_>(d, st, sh);                   \
         } while (0)
         // (256 x 128 tiles on eight waves, one workgroup per CU -- launch_igemm<256, 128, 4, 2, 32, 1, true, ...>, 25 % fewer operand
         //  bytes per flop -- measured 6 % SLOWER than two co-resident 128 x 128 workgroups: DESIGN 7a)
@@ -2188,33 +2192,28 @@ extern "C" int erd_conv_igemm(const erd_conv_desc* d, erd_stream_t stream) {
         bool any_res = false, any_msk = false;
         for (int s = 0; s < d->nseg; ++s) { any_res |= d->seg[s].res != nullptr; any_msk |= d->seg[s].mask != nullptr; }
 #define ERD_X3_EPI(BN_, ST_, GL_)                                                                                                  \
-        (any_res ? (any_msk ? launch_igemm<128, BN_, 4, 1, 32, 2, false, ST_, false, false, true, true, true, GL_>(d, st)         \
-                            : launch_igemm<128, BN_, 4, 1, 32, 2, false, ST_, false, false, true, true, false, GL_>(d, st))       \
-                 : (any_msk ? launch_igemm<128, BN_, 4, 1, 32, 2, false, ST_, false, false, true, false, true, GL_>(d, st)        \
-                            : launch_igemm<128, BN_, 4, 1, 32, 2, false, ST_, false, false, true, false, false, GL_>(d, st)))
+        (any_res ? (any_msk ? launch_igemm<128, BN_, 4, 1, 32, 2, false, ST_, false, false, true, true, true, GL_>(d, st, sh)         \
+                            : launch_igemm<128, BN_, 4, 1, 32, 2, false, ST_, false, false, true, true, false, GL_>(d, st, sh))       \
+                 : (any_msk ? launch_igemm<128, BN_, 4, 1, 32, 2, false, ST_, false, false, true, false, true, GL_>(d, st, sh)        \
+                            : launch_igemm<128, BN_, 4, 1, 32, 2, false, ST_, false, false, true, false, false, GL_>(d, st, sh)))
         // operand slices by LDS-DMA (GL; ERD_IG_GLDS=0: through registers + ds_write, the form of rounds 3-5; bit-identical results)
         const char* const e_glds = getenv("ERD_IG_GLDS");      // (read per launch: tests/test_gpu_f32x3.py flips it inside one process)
         const int glds = e_glds ? atoi(e_glds) : 1;
-        if (glds) {
-            if (seg_taps_any) return ERD_X3_EPI(128, true, true);
-            if (d->Cout <= 64) return ERD_X3_EPI(64, false, true);
-            return ERD_X3_EPI(128, false, true);
-        }
-        if (seg_taps_any) return ERD_X3_EPI(128, true, false);
-        if (d->Cout <= 64) return ERD_X3_EPI(64, false, false);
-        return ERD_X3_EPI(128, false, false);
+#define ERD_X3_GL(BN_, ST_) (glds ? ERD_X3_EPI(BN_, ST_, true) : ERD_X3_EPI(BN_, ST_, false))
+        if (sh.seg_taps) return ERD_X3_GL(128, true);
+        if (d->Cout <= 64) return ERD_X3_GL(64, false);
+        return ERD_X3_GL(128, false);
+#undef ERD_X3_GL
 #undef ERD_X3_EPI
     }
     ERD_REQUIRE(d->w, "conv: this launch needs the fp32 weights (w_x3 serves Cin %% 4 == 0 only)");
-    if (seg_taps_any)   // per-segment tap sets (merged parity classes of a stride-2 input gradient): a dedicated instantiation
-        return launch_igemm<128, 128, 2, 2, 32, 2, false, true>(d, st);
-    if (variant == 9) return launch_igemm<128, 128, 2, 2, 32, 1>(d, st);
-    if (variant == 1) return launch_igemm<128, 128, 2, 2, 16, 3>(d, st);
-    if (variant == 2) return launch_igemm<128, 128, 2, 2, 16, 4>(d, st);
-    if (d->Cout <= 64) return launch_igemm<128, 64, 2, 2, 32, 2>(d, st);
-    int64_t mtiles = 0;
-    for (int s = 0; s < d->nseg; ++s) mtiles += ((int64_t)d->seg[s].N * d->seg[s].GH * d->seg[s].GW + 127) / 128;
-    const int64_t tiles = mtiles * ((d->Cout + 127) / 128);
+    if (sh.seg_taps)   // per-segment tap sets (merged parity classes of a stride-2 input gradient): a dedicated instantiation
+        return launch_igemm<128, 128, 2, 2, 32, 2, false, true>(d, st, sh);
+    if (variant == 9) return launch_igemm<128, 128, 2, 2, 32, 1>(d, st, sh);
+    if (variant == 1) return launch_igemm<128, 128, 2, 2, 16, 3>(d, st, sh);
+    if (variant == 2) return launch_igemm<128, 128, 2, 2, 16, 4>(d, st, sh);
+    if (d->Cout <= 64) return launch_igemm<128, 64, 2, 2, 32, 2>(d, st, sh);
+    const int64_t tiles = sh.mtiles * ((d->Cout + 127) / 128);
     // short K loops, or so many tiles that tile-granular dispatch is already balanced: four small workgroups per
     // CU hide each other's staging/barrier phases best (measured 136 vs 131 TF on 8192 tiles x K=2048)
     // K = 256 onto >= 512 output channels (layer3's expanding 1x1 convolutions and the input gradients of its reducing ones):
@@ -2223,15 +2222,15 @@ extern "C" int erd_conv_igemm(const erd_conv_desc* d, erd_stream_t stream) {
     // equal or worse).  ERD_IGEMM_SHORTK=0: off (A/B aid).
     static const int force = getenv("ERD_IG_FORCE") ? atoi(getenv("ERD_IG_FORCE")) : 0;      // experiment: one variant for every short-K launch
     if (force && d->ntaps * d->Cin <= 256) {
-        if (force == 1) return launch_igemm<128, 128, 2, 2, 32, 2>(d, st);
-        if (force == 2) return launch_igemm<128, 128, 2, 2, 16, 3>(d, st);
-        if (force == 3) return launch_igemm<128, 128, 2, 2, 16, 4>(d, st);
-        if (force == 4) return launch_igemm<128, 64, 2, 2, 32, 2>(d, st);
-        if (force == 5) return launch_igemm<128, 64, 2, 2, 16, 4>(d, st);
-        if (force == 6) return launch_igemm<128, 64, 2, 2, 32, 3>(d, st);
+        if (force == 1) return launch_igemm<128, 128, 2, 2, 32, 2>(d, st, sh);
+        if (force == 2) return launch_igemm<128, 128, 2, 2, 16, 3>(d, st, sh);
+        if (force == 3) return launch_igemm<128, 128, 2, 2, 16, 4>(d, st, sh);
+        if (force == 4) return launch_igemm<128, 64, 2, 2, 32, 2>(d, st, sh);
+        if (force == 5) return launch_igemm<128, 64, 2, 2, 16, 4>(d, st, sh);
+        if (force == 6) return launch_igemm<128, 64, 2, 2, 32, 3>(d, st, sh);
     }
     static const int shortk = getenv("ERD_IGEMM_SHORTK") ? atoi(getenv("ERD_IGEMM_SHORTK")) : 1;
-    if (shortk && d->ntaps * d->Cin == 256 && d->Cout >= 512) return launch_igemm<128, 64, 2, 2, 32, 2>(d, st);
+    if (shortk && d->ntaps * d->Cin == 256 && d->Cout >= 512) return launch_igemm<128, 64, 2, 2, 32, 2>(d, st, sh);
     if (d->ntaps * d->Cin <= 256) {
         // Tile-parallel launches finish in whole dispatch rounds: pick the co-residency whose LAST round is fullest.
         // cost = rounds x (workgroups per CU / steady-state efficiency at that co-residency: 0.83 / 0.85 / 0.87 measured)
@@ -2240,12 +2239,12 @@ extern "C" int erd_conv_igemm(const erd_conv_desc* d, erd_stream_t stream) {
         const double c2 = (double)((tiles + 2 * cus - 1) / (2 * cus)) * (2.0 / 0.83);
         const double c3 = (double)((tiles + 3 * cus - 1) / (3 * cus)) * (3.0 / 0.85);
         const double c4 = (double)((tiles + 4 * cus - 1) / (4 * cus)) * (4.0 / 0.87);
-        if (pick && c3 < c4 && c3 <= c2) return launch_igemm<128, 128, 2, 2, 16, 3>(d, st);
-        if (pick && c2 < c4 && c2 < c3) return launch_igemm<128, 128, 2, 2, 32, 2>(d, st);
-        return launch_igemm<128, 128, 2, 2, 16, 4>(d, st);
+        if (pick && c3 < c4 && c3 <= c2) return launch_igemm<128, 128, 2, 2, 16, 3>(d, st, sh);
+        if (pick && c2 < c4 && c2 < c3) return launch_igemm<128, 128, 2, 2, 32, 2>(d, st, sh);
+        return launch_igemm<128, 128, 2, 2, 16, 4>(d, st, sh);
     }
-    if (tiles >= 16 * 2 * num_cus()) return launch_igemm<128, 128, 2, 2, 16, 4>(d, st);
-    return launch_igemm<128, 128, 2, 2, 32, 2>(d, st);
+    if (tiles >= 16 * 2 * num_cus()) return launch_igemm<128, 128, 2, 2, 16, 4>(d, st, sh);
+    return launch_igemm<128, 128, 2, 2, 32, 2>(d, st, sh);
 }
 
 namespace {
