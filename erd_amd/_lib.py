@@ -56,6 +56,13 @@ class WgradDesc(C.Structure):
                 ("ngroups", i32), ("gx", C.c_void_p * ERD_MAX_GROUPS), ("gdz", C.c_void_p * ERD_MAX_GROUPS)]
 
 
+class ConvGroupedDesc(C.Structure):
+    _fields_ = [("inp", C.c_void_p), ("out", C.c_void_p), ("w", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
+                ("res", C.c_void_p), ("mask", C.c_void_p), ("colsum", C.c_void_p), ("colsum_copies", i32),
+                ("N", i32), ("IH", i32), ("IW", i32), ("OH", i32), ("OW", i32),
+                ("C", i32), ("cg", i32), ("stride", i32), ("relu", i32)]
+
+
 class WgradReduceGroups(C.Structure):
     _fields_ = [("ngroups", i32), ("w", C.c_void_p * ERD_MAX_GROUPS), ("rowscale", C.c_void_p * ERD_MAX_GROUPS),
                 ("dW", C.c_void_p * ERD_MAX_GROUPS), ("rowdot", C.c_void_p * ERD_MAX_GROUPS)]
@@ -103,6 +110,10 @@ _SIGNATURES = {
     "erd_wino_x3_gn_ws_bytes": [P, i32, i32],
     "erd_conv_wgrad": [C.POINTER(WgradDesc), P],
     "erd_wgrad_row3_slices": [C.POINTER(WgradDesc)],
+    "erd_conv_grouped_fwd": [C.POINTER(ConvGroupedDesc), P],
+    "erd_conv_grouped_dgrad": [C.POINTER(ConvGroupedDesc), P],
+    "erd_conv_grouped_wgrad": [P, P, P, i32, i32, i32, i32, i32, i32, i32, P],
+    "erd_conv_grouped_wgrad_splits": [i32, i32, i32, i32, i32, i32],
     "erd_wgrad_reduce": [P, i32, i32, i32, P, P, P, i32, P, P],
     "erd_wgrad_reduce_rows": [P, i32, i32, i32, i32, P, i32, P],
     "erd_wgrad_reduce_grouped": [P, i32, i32, i32, C.POINTER(WgradReduceGroups), i32, P],

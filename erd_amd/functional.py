@@ -201,7 +201,11 @@ class _WgradGroups:
         self.launches = []           # members per launch (diagnostic; the tests read it)
 
     @staticmethod
-    def takes(xin: Tensor, dz: Tensor) -> bool:
+    def takes(xin: Tensor, dz: Tensor, cardinality: int = 1) -> bool:
+        # (a grouped convolution -- ResNeXt conv2, cardinality > 1 -- launches its own weight gradient: the grouped LAUNCHES are forms
+        #  of the three-limb GEMM kernels)
+        if cardinality > 1:
+            return False
         # (not while a whole-step graph is warmed up or captured: the captured step keeps one launch per block -- with grouped
         #  launches in the capture the replayed step left the eager one after the first update, EXPERIMENTS 7n)
         return WGRAD_GROUPED and CAPTURE_ORIGIN is None and K.COMPUTE == "f32x3" and K.WGRAD_X3 and K.WGRAD_X3_GENERIC and xin.dtype == torch.float32 \
@@ -393,18 +397,22 @@ class ConvBNAct(Function):
         dy = dy.contiguous()
         dz, dbeta = K.relu_bwd_colsum(out if relu else None, dy, relu, want_colsum=need_g or need_b)
         wk = ohwi(w)
+        card = x.shape[3] // w.shape[1]      # convolution groups (ResNeXt conv2), from the OIHW parameter
         dW = dgamma = None
         fork = _Fork(x.device)
         if need_w or need_g:
             rowdot = K.zeros_f32(scale.numel(), scale.device) if need_g else None
             dgamma = torch.empty_like(scale) if need_g else None
             with fork:
-                part, S = K.conv_wgrad_partials([x], [dz], k, stride, pad)
+                part, S = K.conv_wgrad_partials([x], [dz], k, stride, pad, cardinality=card)
                 dW = _emit_wgrad(w, part, S, wk, scale, rowdot)
                 if need_g:
                     K.bn_dgamma(rowdot, dbeta, mean, var, eps, out=dgamma)
         dx = None
-        if need_x:
+        if need_x and card > 1:      # the grouped kernel reads the parameter and the row scale directly
+            dx = torch.empty_like(x)
+            K.conv_dgrad([dz], wk, [dx], k, stride, pad, cardinality=card, rowscale=scale)
+        elif need_x:
             wt = K.weight_transpose(wk, scale)
             # a strided 1x1 (projection shortcut) reaches only the even pixels: the rest of dx is zero
             dx = torch.zeros_like(x) if k < stride else torch.empty_like(x)
@@ -484,7 +492,9 @@ def _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_p, need_x, stride, e
     dev = x.device
     grads = [None] * (5 * len(P))
 
-    def wgrad(idx, xin, dz, k, s, pad, scale, dbeta, collect=True):
+    card2 = o1.shape[3] // P[1][0].shape[1]      # conv2's convolution groups (ResNeXt), from the OIHW parameter; 1: ResNet
+
+    def wgrad(idx, xin, dz, k, s, pad, scale, dbeta, collect=True, card=1):
         """dW (scaled by the folded BN), d gamma, d beta of conv `idx`"""
         w, g, b, m, v = P[idx]
         base = 5 * idx
@@ -493,7 +503,7 @@ def _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_p, need_x, stride, e
         wk = ohwi(w)
         trail = None
         sunk = all((not need_p[base + q]) or _sink(t) is not None for q, t in enumerate((w, g, b)))
-        if collect and groups is not None and sunk and need_p[base] and groups.takes(xin, dz):
+        if collect and groups is not None and sunk and need_p[base] and groups.takes(xin, dz, card):
             groups.add(lambda: wgrad(idx, xin, dz, k, s, pad, scale, dbeta, collect=False), xin, dz, k, s, pad, scale, dbeta, (w, g, b, m, v),
                        tuple(need_p[base:base + 3]))
             return
@@ -501,13 +511,13 @@ def _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_p, need_x, stride, e
             trail = _Trail(dev, xin, dz, scale, dbeta)
             trail.__enter__()
         try:
-            _wgrad_body(idx, xin, dz, k, s, pad, scale, dbeta, w, g, b, m, v, base, wk)
+            _wgrad_body(idx, xin, dz, k, s, pad, scale, dbeta, w, g, b, m, v, base, wk, card)
         finally:
             if trail is not None:
                 trail.__exit__(None, None, None)
 
-    def _wgrad_body(idx, xin, dz, k, s, pad, scale, dbeta, w, g, b, m, v, base, wk):
-        part, S = K.conv_wgrad_partials([xin], [dz], k, s, pad)
+    def _wgrad_body(idx, xin, dz, k, s, pad, scale, dbeta, w, g, b, m, v, base, wk, card=1):
+        part, S = K.conv_wgrad_partials([xin], [dz], k, s, pad, cardinality=card)
         rowdot = K.zeros_f32(scale.numel(), scale.device) if need_p[base + 1] else None
         grads[5 * idx] = _emit_wgrad(w, part, S, wk, scale, rowdot)
         if need_p[base + 1]:
@@ -542,10 +552,13 @@ def _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_p, need_x, stride, e
     rep_slot = lambda n: K.zeros_f32(K.colsum_copies(n) * n, dev).view(K.colsum_copies(n), n)
     db2 = rep_slot(o2.shape[3])
     K.conv_dgrad([dz3], K.weight_transpose(ohwi(P[2][0]), s3), [dz2], 1, 1, 0, relu_mask=[o2], colsum=db2)
-    wgrad(1, o1, dz2, 3, stride, 1, s2, db2)
+    wgrad(1, o1, dz2, 3, stride, 1, s2, db2, card=card2)
     dz1 = torch.empty_like(o1)
     db1 = rep_slot(o1.shape[3])
-    K.conv_dgrad([dz2], K.weight_transpose(ohwi(P[1][0]), s2), [dz1], 3, stride, 1, relu_mask=[o1], colsum=db1)
+    if card2 > 1:      # the grouped kernel reads the parameter and the row scale directly (no transposed copy to keep fresh)
+        K.conv_dgrad([dz2], ohwi(P[1][0]), [dz1], 3, stride, 1, relu_mask=[o1], colsum=db1, cardinality=card2, rowscale=s2)
+    else:
+        K.conv_dgrad([dz2], K.weight_transpose(ohwi(P[1][0]), s2), [dz1], 3, stride, 1, relu_mask=[o1], colsum=db1)
     wgrad(0, x, dz1, 1, 1, 0, s1, db1)
     dx = None
     if need_x:

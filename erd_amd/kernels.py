@@ -420,6 +420,9 @@ def conv_forward(xs: Sequence[Tensor], w: Tensor, outs: Sequence[Tensor], k: int
     """outs[i] = epi(conv(xs[i], w)); w is [Cout,k,k,Cin] contiguous (OHWI).  All segments share w."""
     _require_gpu(w, *xs, *outs)
     Cout, Cin = w.shape[0], w.shape[3]
+    if Cin != xs[0].shape[3]:       # a grouped weight [Cout, k, k, Cin / cardinality] (before Winograd, which looks at w.shape[3])
+        _conv_grouped_forward(xs, w, outs, k, stride, pad, scale, shift, res, alphas, relu)
+        return
     if alphas is None and wino_ok(Cin, k, stride, pad) and w.shape[1] == 3 and (WINO_TRAIN_FWD if RECORDED else WINO_NOGRAD_FWD):
         wino_conv3x3(xs, _wino_weights_cached(w), outs, Cout, scale=scale, shift=shift, relu=relu, res=res)
         return
@@ -471,6 +474,106 @@ def conv_forward(xs: Sequence[Tensor], w: Tensor, outs: Sequence[Tensor], k: int
     _attach_sk_ws(d, w.device)
     _timed_call(_igemm_class(d, "fwd"), flop, "erd_conv_igemm", C.byref(d), _stream(), nbytes=nbytes if _TIMING is not None else 0.0,
                 tag=tag if TIMING_DETAIL else "")
+
+
+# ---------------------------------------------------------------------------------------------
+# grouped 3x3 convolutions (ResNeXt conv2, resnext.py:55-64; csrc/conv_grouped.hip).  "cardinality" = the convolution's groups,
+# "cg" = channels per group ("group" alone means a grouped weight-gradient LAUNCH in this code base).  One plain NHWC fp32 map per
+# launch; the same fp32 launches serve the compute modes "f32" and "f32x3".
+# ---------------------------------------------------------------------------------------------
+GROUPED_CG = (4, 8, 16, 32)
+
+
+def _grouped_mode_check(what: str, *ts) -> None:
+    if COMPUTE == "bf16" or any(t is not None and t.dtype != torch.float32 for t in ts):
+        raise NotImplementedError(f"{what}: grouped convolutions (cardinality > 1) are not built for the compute mode 'bf16' "
+                                  "(--amp, maps stored as bf16); use 'f32x3' or 'f32'")
+
+
+def _grouped_desc(key, inp: Tensor, out: Tensor, x_like: Tensor, z_like: Tensor, cg: int, stride: int, extras):
+    """cached descriptor of a grouped forward / input-gradient launch (pointers left to the caller); x_like / z_like: the maps with
+    the geometry of the layer's input and output"""
+    cache = _desc_cache()
+    ent = cache.get(key)
+    if ent is None:
+        for t in (inp, out, *extras):
+            if t is not None:
+                _check_map(t)
+                assert t.is_contiguous(), "grouped convolutions take dense NHWC maps"
+        N, IH, IW, Cc = x_like.shape
+        assert Cc % cg == 0 and z_like.shape == (N, conv_out_size(IH, 3, stride, 1), conv_out_size(IW, 3, stride, 1), Cc), \
+            (tuple(x_like.shape), tuple(z_like.shape), cg, stride)
+        d = _lib.ConvGroupedDesc()
+        d.N, d.IH, d.IW, d.OH, d.OW = N, IH, IW, z_like.shape[1], z_like.shape[2]
+        d.C, d.cg, d.stride = Cc, cg, stride
+        flop = 2.0 * z_like.shape[0] * z_like.shape[1] * z_like.shape[2] * Cc * 9 * cg
+        nbytes = 4.0 * (inp.numel() + out.numel() + Cc * 9 * cg)
+        ent = cache[key] = (d, flop, nbytes, f"px{out.shape[0] * out.shape[1] * out.shape[2]} {Cc}/{Cc // cg} k3s{stride}")
+    return ent
+
+
+def _conv_grouped_forward(xs, w: Tensor, outs, k: int, stride: int, pad: int, scale, shift, res, alphas, relu: bool) -> None:
+    """outs[0] = [relu](conv_g(xs[0], w) * scale + shift [+ res]); w is the parameter's own layout [C, 3, 3, cg]"""
+    if len(xs) != 1 or alphas is not None or k != 3 or pad != 1:
+        raise ValueError("grouped convolution: one map, 3x3, pad 1 (ResNeXt conv2)")
+    x, out = xs[0], outs[0]
+    r = None if res is None else res[0]
+    _grouped_mode_check("conv_forward", x, out, r, w)
+    cg = w.shape[3]
+    assert w.is_contiguous() and w.shape[0] == x.shape[3] and w.shape[1] == 3 and w.shape[2] == 3, tuple(w.shape)
+    key = ("gfwd", stride, relu, w.shape, _geom((x, out, r)), scale is not None, shift is not None)
+    d, flop, nbytes, tag = _grouped_desc(key, x, out, x, out, cg, stride, (r,))
+    d.inp, d.out, d.w = x.data_ptr(), out.data_ptr(), w.data_ptr()
+    d.scale = 0 if scale is None else scale.data_ptr()
+    d.shift = 0 if shift is None else shift.data_ptr()
+    d.res = 0 if r is None else r.data_ptr()
+    d.mask, d.colsum, d.colsum_copies = 0, 0, 0
+    d.relu = 1 if relu else 0
+    _timed_call("conv_grouped", flop, "erd_conv_grouped_fwd", C.byref(d), _stream(), nbytes=nbytes if _TIMING is not None else 0.0,
+                tag=tag if TIMING_DETAIL else "")
+
+
+def _conv_grouped_dgrad(dz: Tensor, w: Tensor, dx: Tensor, stride: int, rowscale, accumulate: bool, res, relu_mask, colsum) -> None:
+    """dx (=|+=) conv_g^T(dz, w * rowscale) [+ res], zeroed where relu_mask <= 0, column sums into `colsum`.  w is the PARAMETER's layout
+    [C, 3, 3, cg] and rowscale the folded BN row scale: the kernel scales and transposes while it stages the weights, so there is no
+    prepared copy an optimizer update could leave stale.  Every pixel of dx is written."""
+    _grouped_mode_check("conv_dgrad", dz, dx, res, relu_mask, w)
+    cg = w.shape[3]
+    assert w.is_contiguous() and w.shape[0] == dx.shape[3] and w.shape[1] == 3 and w.shape[2] == 3, tuple(w.shape)
+    r = dx if accumulate else res
+    key = ("gdgrad", stride, w.shape, _geom((dz, dx, r, relu_mask)), rowscale is not None, None if colsum is None else colsum.numel())
+    d, flop, nbytes, tag = _grouped_desc(key, dz, dx, dx, dz, cg, stride, (r, relu_mask))
+    d.inp, d.out, d.w = dz.data_ptr(), dx.data_ptr(), w.data_ptr()
+    d.scale = 0 if rowscale is None else rowscale.data_ptr()
+    d.shift, d.relu = 0, 0
+    d.res = 0 if r is None else r.data_ptr()
+    d.mask = 0 if relu_mask is None else relu_mask.data_ptr()
+    d.colsum = 0 if colsum is None else colsum.data_ptr()
+    d.colsum_copies = 0 if colsum is None else colsum.numel() // dx.shape[3]
+    _timed_call("conv_grouped", flop, "erd_conv_grouped_dgrad", C.byref(d), _stream(), nbytes=nbytes if _TIMING is not None else 0.0,
+                tag=(tag + " dgrad") if TIMING_DETAIL else "")
+
+
+def _conv_grouped_wgrad_partials(x: Tensor, dz: Tensor, stride: int, cardinality: int):
+    """(part [S, C, 9 * cg], S): split slabs over the pixel axis, no atomics; wgrad_reduce folds them with K = 9 * cg.
+    S: one dispatch round of the usable CUs over the launch's channel blocks (erd_conv_grouped_wgrad_splits)."""
+    _grouped_mode_check("conv_wgrad_partials", x, dz)
+    _check_map(x)
+    _check_map(dz)
+    assert x.is_contiguous() and dz.is_contiguous(), "grouped convolutions take dense NHWC maps"
+    N, IH, IW, Cc = x.shape
+    cg = Cc // cardinality
+    assert cg * cardinality == Cc and dz.shape == (N, conv_out_size(IH, 3, stride, 1), conv_out_size(IW, 3, stride, 1), Cc)
+    npix = dz.shape[0] * dz.shape[1] * dz.shape[2]
+    S = int(_lib.load().erd_conv_grouped_wgrad_splits(N, IH, IW, Cc, cg, stride))      # one dispatch round of erd_usable_cus()
+    if S < 1:
+        raise _lib.ErdHipError(f"erd_conv_grouped_wgrad_splits: {_lib.load().erd_last_error().decode(errors='replace')}")
+    part = ws_float("wgrad_part", S * Cc * 9 * cg, x.device)
+    flop = 2.0 * npix * Cc * 9 * cg
+    nbytes = 4.0 * (x.numel() + dz.numel() + S * Cc * 9 * cg)
+    _timed_call("conv_grouped_wgrad", flop, "erd_conv_grouped_wgrad", _p(x), _p(dz), _p(part), N, IH, IW, Cc, cg, stride, S, _stream(),
+                nbytes=nbytes if _TIMING is not None else 0.0, tag=f"px{npix} {Cc}/{cardinality} k3s{stride} S{S}" if TIMING_DETAIL else "")
+    return part, S
 
 
 WINOGRAD = _os.environ.get("ERD_WINO", "1") != "0"     # F(2x2,3x3) for the fp32 3x3 stride-1 convolutions (winograd.hip)
@@ -759,13 +862,23 @@ def weight_transpose(w: Tensor, rowscale: Optional[Tensor] = None) -> Tensor:
 
 def conv_dgrad(dzs: Sequence[Tensor], wt: Tensor, dxs: Sequence[Tensor], k: int, stride: int, pad: int,
                accumulate: bool = False, res: Optional[Sequence[Tensor]] = None,
-               relu_mask: Optional[Sequence[Tensor]] = None, colsum: Optional[Tensor] = None) -> None:
+               relu_mask: Optional[Sequence[Tensor]] = None, colsum: Optional[Tensor] = None, cardinality: int = 1,
+               rowscale: Optional[Tensor] = None) -> None:
     """dxs[i] (+)= conv_transpose(dzs[i]); wt = weight_transpose(w) is [Cin,k,k,Cout].
+    cardinality > 1 (a grouped 3x3 convolution, one map): `wt` is the UNTRANSPOSED parameter view [C,3,3,cg] and `rowscale` the folded
+    BN row scale -- the grouped kernel transposes and scales as it stages the weights, and writes every pixel of dx.
     colsum: [Cin] or a replicated [copies, Cin] accumulator (copies a power of two; bn_dgamma folds the rows).
     stride 1: one launch; stride 2: one launch per output-parity class (no zero-multiplies).
     Pixels of dx that no tap reaches (k=1, stride 2) are NOT written: pass accumulate=True on a
     buffer that already holds the other branch's gradient, or zero it first."""
     _require_gpu(wt, *dzs, *dxs)
+    if cardinality > 1:
+        if len(dzs) != 1 or k != 3 or pad != 1:
+            raise ValueError("grouped convolution: one map, 3x3, pad 1 (ResNeXt conv2)")
+        _conv_grouped_dgrad(dzs[0], wt, dxs[0], stride, rowscale, accumulate, None if res is None else res[0],
+                            None if relu_mask is None else relu_mask[0], colsum)
+        return
+    assert rowscale is None, "conv_dgrad: a row scale goes into weight_transpose (cardinality 1)"
     Cin, Cout = wt.shape[0], wt.shape[3]       # of the forward conv
     if wt.dtype == torch.float32 and WINO_DGRAD and wino_ok(Cout, k, stride, pad):
         # the input gradient of a 3x3 stride-1 conv is a 3x3 stride-1 conv of dz with the flipped transposed weights
@@ -951,10 +1064,15 @@ def _extent(t: Tensor):
     return t.data_ptr(), last + 1
 
 
-def conv_wgrad_partials(xs: Sequence[Tensor], dzs: Sequence[Tensor], k: int, stride: int, pad: int):
+def conv_wgrad_partials(xs: Sequence[Tensor], dzs: Sequence[Tensor], k: int, stride: int, pad: int, cardinality: int = 1):
     """returns (part [S, Cout, k*k, Cin], S): split-K partial slabs.  All segments (maps sharing the weights, e.g.
-    the head's five levels) are summed in ONE launch: their pixels are concatenated along the GEMM K axis."""
+    the head's five levels) are summed in ONE launch: their pixels are concatenated along the GEMM K axis.
+    cardinality > 1 (a grouped 3x3 convolution, one map): part is [S, C, 9, C / cardinality]."""
     _require_gpu(*xs, *dzs)
+    if cardinality > 1:
+        if len(xs) != 1 or k != 3 or pad != 1:
+            raise ValueError("grouped convolution: one map, 3x3, pad 1 (ResNeXt conv2)")
+        return _conv_grouped_wgrad_partials(xs[0], dzs[0], stride, cardinality)
     xb = min(x.data_ptr() for x in xs)
     zb = min(z.data_ptr() for z in dzs)
     xoff = tuple((x.data_ptr() - xb) // x.element_size() for x in xs)

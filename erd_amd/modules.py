@@ -43,10 +43,11 @@ def _conv_weight(cout: int, cin: int, k: int) -> nn.Parameter:
 
 
 class ConvHolder(nn.Module):
-    def __init__(self, cin: int, cout: int, k: int, stride: int = 1, padding: int = 0, bias: bool = False):
+    def __init__(self, cin: int, cout: int, k: int, stride: int = 1, padding: int = 0, bias: bool = False, groups: int = 1):
         super().__init__()
         self.in_channels, self.out_channels, self.k, self.stride, self.padding = cin, cout, k, stride, padding
-        self.weight = _conv_weight(cout, cin, k)
+        self.groups = groups            # convolution groups (ResNeXt conv2): the weight is [cout, cin / groups, k, k]
+        self.weight = _conv_weight(cout, cin // groups, k)
         self.bias = nn.Parameter(torch.zeros(cout)) if bias else None
         self.reset_parameters()
 
@@ -162,13 +163,21 @@ def _resolve_pretrained(checkpoint: str) -> Optional[str]:
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes: int, planes: int, stride: int, downsample: bool, bn_requires_grad: bool = True):
+    GROUPED_CG = (4, 8, 16, 32)      # channels per group the grouped kernels take (csrc/conv_grouped.hip)
+
+    def __init__(self, inplanes: int, planes: int, stride: int, downsample: bool, bn_requires_grad: bool = True,
+                 groups: int = 1, base_width: int = 4, base_channels: int = 64):
         super().__init__()
-        self.conv1 = ConvHolder(inplanes, planes, 1)
-        self.bn1 = FrozenStatBN(planes, requires_grad=bn_requires_grad)
-        self.conv2 = ConvHolder(planes, planes, 3, stride, 1)     # style='pytorch': stride on the 3x3
-        self.bn2 = FrozenStatBN(planes, requires_grad=bn_requires_grad)
-        self.conv3 = ConvHolder(planes, planes * 4, 1)
+        # ResNeXt (resnext.py:29-33): conv1 / conv2 / conv3 run at `width`, conv2 in `groups` groups; groups = 1 is the ResNet block
+        width = planes if groups == 1 else math.floor(planes * (base_width / base_channels)) * groups
+        if groups > 1 and width // groups not in self.GROUPED_CG:
+            raise NotImplementedError(f"ResNeXt Bottleneck(planes={planes}, groups={groups}, base_width={base_width}): conv2 has "
+                                      f"{width // groups} channels per group; supported: {', '.join(map(str, self.GROUPED_CG))}")
+        self.conv1 = ConvHolder(inplanes, width, 1)
+        self.bn1 = FrozenStatBN(width, requires_grad=bn_requires_grad)
+        self.conv2 = ConvHolder(width, width, 3, stride, 1, groups=groups)     # style='pytorch': stride on the 3x3
+        self.bn2 = FrozenStatBN(width, requires_grad=bn_requires_grad)
+        self.conv3 = ConvHolder(width, planes * 4, 1)
         self.bn3 = FrozenStatBN(planes * 4, requires_grad=bn_requires_grad)
         self.stride = stride
         self.downsample = None
@@ -235,12 +244,16 @@ class ResNet(nn.Module):
             planes = 64 * 2 ** i
             blocks = []
             for b in range(nblk):
-                blocks.append(Bottleneck(inplanes, planes, strides[i] if b == 0 else 1, b == 0, bn_rg))
+                blocks.append(Bottleneck(inplanes, planes, strides[i] if b == 0 else 1, b == 0, bn_rg, **self._block_kwargs()))
                 inplanes = planes * 4
             name = f"layer{i + 1}"
             self.add_module(name, nn.Sequential(*blocks))
             self.res_layers.append(name)
         self._freeze_stages()
+
+    def _block_kwargs(self) -> dict:
+        """what a subclass adds to every Bottleneck (ResNeXt: groups / base_width)"""
+        return {}
 
     def _freeze_stages(self):
         """resnet.py:613-629."""
@@ -348,6 +361,26 @@ class ResNet(nn.Module):
         for m in mods:
             out += [t for _, t in sorted(m.state_dict().items()) if t.dtype == torch.float32]
         return out
+
+
+@MODELS.register_module()
+class ResNeXt(ResNet):
+    """ResNeXt (mmdet/models/backbones/resnext.py:109-154): the ResNet whose bottlenecks run conv1 / conv2 / conv3 at
+    width = floor(planes * base_width / 64) * groups with conv2 a 3x3 convolution in `groups` groups (resnext.py:29-33, 55-64).
+    State-dict keys and shapes are the reference's (`layerX.Y.conv2.weight` is [width, width / groups, 3, 3]); groups = 1 is exactly
+    ResNet.  conv2 runs on the grouped kernels (csrc/conv_grouped.hip), which take 4, 8, 16 or 32 channels per group -- the 32x4d and
+    64x4d families; anything else raises NotImplementedError here.
+
+    init_cfg 'open-mmlab://resnext101_32x4d' / 'open-mmlab://resnext101_64x4d' resolve like the torchvision names, on disk only
+    ($ERD_PRETRAINED_DIR, then torch hub's checkpoint directory), and raise when absent.  The canonical file names of the open-mmlab
+    model zoo are not recorded in this tree, so the `<name>*.pth` glob with its warning is the rule for them."""
+
+    def __init__(self, groups: int = 1, base_width: int = 4, **kwargs):
+        self.groups, self.base_width = int(groups), int(base_width)
+        super().__init__(**kwargs)
+
+    def _block_kwargs(self) -> dict:
+        return dict(groups=self.groups, base_width=self.base_width)
 
 
 # ---------------------------------------------------------------------------------------------------

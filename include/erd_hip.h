@@ -256,6 +256,43 @@ typedef struct {
 int erd_wgrad_reduce_grouped(const float* part, int nsplit, int Cout, int K, const erd_wgrad_reduce_groups* groups,
                              int accumulate, erd_stream_t stream);
 
+/* ---- grouped 3x3 convolution (ResNeXt conv2) on the fp32 vector pipe, csrc/conv_grouped.hip ----
+ * `cardinality` independent 3x3 / pad 1 / stride 1 | 2 convolutions of cg = C / cardinality channels each, Cin == Cout == C,
+ * cg in {4, 8, 16, 32}, cardinality >= 2, ONE dense NHWC fp32 map per launch; anything else: ERD_EUNSUPPORTED / ERD_EINVAL.
+ * w is the parameter's own layout [C][3][3][cg].  Every product-sum is one fp32 fma chain in an order fixed by the shape
+ * (the group's channel quads ascending, per quad the taps ascending, per tap the quad's four channels; a tap outside the map
+ * contributes an operand of 0): results do not depend on the grid or the CU reserve, and the compute modes "f32" and "f32x3"
+ * share these launches.  Maps hold fewer than 2^31 elements.  x is [N][IH][IW][C], z / dz are
+ * [N][OH][OW][C] with OH = (IH - 1) / stride + 1; all pointers 16-byte aligned.
+ *   fwd    out = z = [relu](conv_g(in = x, w) * scale + shift [+ res]); scale, shift, res, relu optional; mask / colsum unused
+ *   dgrad  out = dx = conv_g^T(in = dz, w * scale) [+ res], zeroed where mask <= 0; `scale` is the folded BN ROW scale [C] of the
+ *          forward layer (optional), applied while the weights are staged; res / mask have dx's geometry (res may alias out:
+ *          accumulation); EVERY pixel of dx is written, also at stride 2; colsum: optional [colsum_copies][C] accumulator (+= column
+ *          sums of the stored dx, float atomics, workgroup b adds into row b mod copies; copies 0 / 1 or a power of two)
+ * replaces: the F.conv2d(groups=) dispatch of resnext.py:55-64 (conv2 of the ResNeXt Bottleneck) and its convolution_backward. */
+typedef struct {
+    const float* in;
+    float* out;
+    const float* w;
+    const float* scale;
+    const float* shift;
+    const float* res;
+    const float* mask;
+    float* colsum;
+    int colsum_copies;
+    int N, IH, IW, OH, OW;
+    int C, cg, stride, relu;
+} erd_conv_grouped_desc;
+int erd_conv_grouped_fwd(const erd_conv_grouped_desc* d, erd_stream_t stream);
+int erd_conv_grouped_dgrad(const erd_conv_grouped_desc* d, erd_stream_t stream);
+/* weight-gradient partial slabs part[s][C][9][cg] = sum over the pixels of split s (a contiguous pixel range; no atomics, the
+ * summation order is fixed by the shape and nsplit) of dz[p][co] * x[p shifted by tap][group(co) * cg + ci]: erd_wgrad_reduce folds
+ * them with K = 9 * cg (row scale, <W, G> dots, accumulation into the flat slot).  nsplit in [1, 4096];
+ * erd_conv_grouped_wgrad_splits returns the count that makes one dispatch round of erd_usable_cus() (< 0: shape out of scope). */
+int erd_conv_grouped_wgrad(const float* x, const float* dz, float* part, int N, int IH, int IW, int C, int cg, int stride,
+                           int nsplit, erd_stream_t stream);
+int erd_conv_grouped_wgrad_splits(int N, int IH, int IW, int C, int cg, int stride);
+
 /* dst[ci][t'][co] = rowscale[co] * w[co][t][ci]  (t' = flip ? ntaps-1-t : t): weights of the
  * input-gradient convolution. */
 int erd_weight_transpose(const float* w, const float* rowscale, float* dst, int Cout, int ntaps,
