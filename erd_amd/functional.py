@@ -70,6 +70,10 @@ WGRAD_TRAIL = _os.environ.get('ERD_WGRAD_TRAIL', '1') != '0'
 # G times longer K loops per workgroup, G times fewer partial-slab bytes and reduce launches (_WgradGroups).  0: every block
 # launches its own as it goes (A/B aid).
 WGRAD_GROUPED = _os.environ.get('ERD_WGRAD_GROUPED', '1') != '0'
+# Winograd-domain weight gradients (_wgrad_plain, f32x3): the BN-free 3x3 / stride-1 / pad-1 layers whose channel counts are multiples of
+# 128 -- the head towers' eight launches per step, the FPN output convolutions -- form dW as F(3x3, 2x2): 16 of the direct three-tap
+# kernel's 36 products per tile (K.conv_wgrad_wino / K.wgrad_wino_reduce).  0: the direct kernel everywhere (A/B aid).
+WGRAD_WINO = _os.environ.get('ERD_WGRAD_WINO', '1') != '0'
 WGRAD_GROUP_CAP = 8      # members per launch (erd_hip.h ERD_MAX_GROUPS); also bounds the gradient maps kept alive (R101's layer3: 22 identity blocks)
 RES_LAYER_NODE = _os.environ.get('ERD_RES_LAYER', '1') != '0'    # a whole ResNet stage as one autograd node (ResLayerFn): A/B aid
 HEAD_TRAIL = _os.environ.get('ERD_HEAD_TRAIL', '0') != '0'      # the head towers' weight gradients too (A/B aid: see _wgrad_plain)
@@ -185,6 +189,18 @@ def _emit_wgrad(w: Tensor, part: Tensor, S: int, wk: Tensor, scale: Optional[Ten
         return None
     dWk = torch.empty_like(wk)
     K.wgrad_reduce(part, S, wk, scale, dWk, False, rowdot, rowdot_zeroed=True)
+    return _to_oihw(dWk)
+
+
+def _emit_wgrad_wino(w: Tensor, part: Tensor, S: int, wk: Tensor):
+    """_emit_wgrad for the slabs of K.conv_wgrad_wino: the reduce applies the output transform on the way"""
+    sink = _sink(w)
+    if sink is not None:
+        K.wgrad_wino_reduce(part, S, ohwi(sink), True)
+        _sunk(w)
+        return None
+    dWk = torch.empty_like(wk)
+    K.wgrad_wino_reduce(part, S, dWk, False)
     return _to_oihw(dWk)
 
 
@@ -360,14 +376,22 @@ def _wgrad_plain(w: Tensor, xs, dzs, k: int, stride: int, pad: int, keep=(), tra
     allocations behind the views in xs / dzs (kept alive for the trailing stream).  `trail=False`: the head towers --
     their 0.9 ms weight gradients already alternate with the input gradients on the two tower streams; queued behind each
     other on the ONE trailing stream they become a 7 ms serial tail that the join at the end of backward waits for
-    (measured: 80.0 img/s with them trailing, 80.3 without)."""
+    (measured: 80.0 img/s with them trailing, 80.3 without).  3x3 / stride-1 / pad-1 layers that K.conv_wgrad_wino_ok takes
+    go through the Winograd-domain pair (WGRAD_WINO)."""
     wk = ohwi(w)
+    wino = WGRAD_WINO and (k, stride, pad) == (3, 1, 1) and K.conv_wgrad_wino_ok(xs, dzs)
+
+    def run():
+        if wino:
+            part, S = K.conv_wgrad_wino(xs, dzs)
+            return _emit_wgrad_wino(w, part, S, wk)
+        part, S = K.conv_wgrad_partials(xs, dzs, k, stride, pad)
+        return _emit_wgrad(w, part, S, wk, None, None)
+
     if trail and WGRAD_TRAIL and _sink(w) is not None:
         with _Trail(xs[0].device, *(keep or (list(xs) + list(dzs)))):
-            part, S = K.conv_wgrad_partials(xs, dzs, k, stride, pad)
-            return _emit_wgrad(w, part, S, wk, None, None)
-    part, S = K.conv_wgrad_partials(xs, dzs, k, stride, pad)
-    return _emit_wgrad(w, part, S, wk, None, None)
+            return run()
+    return run()
 
 
 class ConvBNAct(Function):

@@ -1093,6 +1093,66 @@ def conv_wgrad_partials(xs: Sequence[Tensor], dzs: Sequence[Tensor], k: int, str
     return part, S
 
 
+def _wgrad_wino_entry(xs: Sequence[Tensor], dzs: Sequence[Tensor]):
+    """the cached launch descriptor of the Winograd-domain weight gradient of these maps, or None where erd_conv_wgrad_wino_ok refuses"""
+    xb = min(x.data_ptr() for x in xs)
+    zb = min(z.data_ptr() for z in dzs)
+    xoff = tuple((x.data_ptr() - xb) // x.element_size() for x in xs)
+    zoff = tuple((z.data_ptr() - zb) // z.element_size() for z in dzs)
+    cache = _desc_cache()
+    key = ("wgrad_wino", _geom(xs), _geom(dzs), xoff, zoff, COMPUTE, CU_RESERVE)
+    ent = cache.get(key)
+    if ent is None:
+        d, _, flop, nbytes, tag, Cout, Cin, _ = _wgrad_desc(xs, dzs, 3, 1, 1, xoff, zoff)
+        d.limbs3 = 1
+        if COMPUTE != "f32x3" or not int(_lib.load().erd_conv_wgrad_wino_ok(C.byref(d))):
+            ent = cache[key] = (None,)
+        else:
+            # ONE dispatch round of one workgroup per CU: 4 transform rows x (Cout / 128) x (Cin / 128) workgroups per split
+            tiles = sum(dz.shape[0] * ((dz.shape[1] + 1) // 2) * ((dz.shape[2] + 1) // 2) for dz in dzs)
+            comb = 4 * (Cout // 128) * (Cin // 128)
+            steps = (tiles + 15) // 16
+            S = int(max(1, min(_one_round(256) // comb, steps // 4 if steps >= 4 else 1)))
+            nbytes += 4.0 * (S * 16 - d.nsplit * 9) * Cout * Cin      # (the slabs: [S][16] here, [nsplit][9] in the direct form's count)
+            d.nsplit = S
+            ent = cache[key] = (d, S, flop, nbytes, tag.rsplit(" S", 1)[0] + f" S{S} wino", Cout, Cin)
+    return ent, xb, zb
+
+
+def conv_wgrad_wino_ok(xs: Sequence[Tensor], dzs: Sequence[Tensor]) -> bool:
+    """True where conv_wgrad_wino takes these maps (3x3 / stride 1 / pad 1 implied): f32x3, fp32 maps, Cin and Cout multiples of 128"""
+    if COMPUTE != "f32x3" or any(t.dtype != torch.float32 for t in (*xs, *dzs)):
+        return False
+    return _wgrad_wino_entry(xs, dzs)[0][0] is not None
+
+
+def conv_wgrad_wino(xs: Sequence[Tensor], dzs: Sequence[Tensor], nsplit: Optional[int] = None):
+    """returns (part [S, 16, Cout, Cin], S): split-K partial slabs of the 3x3 / stride-1 / pad-1 weight gradient in the Winograd domain
+    F(3x3, 2x2) (erd_conv_wgrad_wino; wgrad_wino_reduce folds them into dW).  All segments in one launch, tiles concatenated along K.
+    Timed under the three-tap class `conv_wgrad_row3`, whose nominal flops (36 products per tile) overstate these launches' 16 by 36/16."""
+    _require_gpu(*xs, *dzs)
+    ent, xb, zb = _wgrad_wino_entry(xs, dzs)
+    if ent[0] is None:
+        raise RuntimeError("conv_wgrad_wino: f32x3 mode, fp32 maps, 3x3 / stride 1 / pad 1, Cin and Cout multiples of 128 only")
+    d, S, flop, nbytes, tag, Cout, Cin = ent
+    if nsplit is not None:
+        S = int(nsplit)
+    d.nsplit = S
+    d.x, d.dz = xb, zb
+    part = ws_float("wgrad_part", S * 16 * Cout * Cin, xs[0].device)
+    d.part = part.data_ptr()
+    _timed_call("conv_wgrad_row3", flop, "erd_conv_wgrad_wino", C.byref(d), _stream(), nbytes=nbytes if _TIMING is not None else 0.0,
+                tag=tag if TIMING_DETAIL else "")
+    return part, S
+
+
+def wgrad_wino_reduce(part: Tensor, S: int, dW: Tensor, accumulate: bool) -> None:
+    """dW [Cout, 3, 3, Cin] (+)= At (sum of the S slabs of conv_wgrad_wino, in order) At^T"""
+    Cout, Cin = dW.shape[0], dW.shape[-1]
+    assert dW.numel() == Cout * 9 * Cin and dW.is_contiguous()
+    call("erd_wgrad_wino_reduce", _p(part), S, Cout, Cin, _p(dW), 1 if accumulate else 0, _stream())
+
+
 def _wgrad_desc(xs, dzs, k, stride, pad, xoff, zoff, ngroups: int = 1):
     """the launch descriptor of a weight gradient (base pointers and the partial-slab pointer left to the caller).
     ngroups > 1: xs / dzs are the maps of ONE of `ngroups` independent weight gradients of this geometry that share the launch

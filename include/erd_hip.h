@@ -256,6 +256,21 @@ typedef struct {
 int erd_wgrad_reduce_grouped(const float* part, int nsplit, int Cout, int K, const erd_wgrad_reduce_groups* groups,
                              int accumulate, erd_stream_t stream);
 
+/* ---- weight gradient of a 3x3 / stride 1 / pad 1 convolution in the Winograd domain, F(3x3, 2x2), csrc/wgrad_wino.hip ----
+ * Three-limb form only (fp32 maps, every product from exact three-limb splits, fp32 partial slabs).  Per 2x2 tile of the gradient
+ * map: V = Bt x Bt^T of the 4x4 input patch, M = G dz G^T of the tile, dU[xi] += M[xi] V[xi] over the tiles of all segments
+ * (16 products per tile and channel pair where erd_conv_wgrad's three-tap kernel counts 36); dW = At dU At^T in the reduce.
+ * erd_conv_wgrad_wino takes erd_conv_wgrad's descriptor -- segments, extents, Cin, Cout, the nine taps in order, nsplit; limbs3
+ * is implied, ngroups must be 1 -- and writes part[nsplit][16][Cout][Cin] (every slab whole, deterministic for a given nsplit).
+ * It refuses (ERD_EINVAL, before any launch) bf16-stored maps or bf16 multiplicands, Cin or Cout that are not multiples of 128,
+ * strides other than 1 and every layer that is not 3x3 / pad 1.  erd_conv_wgrad_wino_ok: 1 if the descriptor is taken (the
+ * host's routing predicate), else 0.
+ * erd_wgrad_wino_reduce: dW[Cout][9][Cin] (+)= At (sum_s part[s]) At^T, slabs summed in order; accumulate: bit 0 = add into dW.
+ * No rowscale / rowdot: only convolutions without BN coupling are routed here. */
+int erd_conv_wgrad_wino(const erd_wgrad_desc* d, erd_stream_t stream);
+int erd_conv_wgrad_wino_ok(const erd_wgrad_desc* d);
+int erd_wgrad_wino_reduce(const float* part, int nsplit, int Cout, int Cin, float* dW, int accumulate, erd_stream_t stream);
+
 /* ---- grouped 3x3 convolution (ResNeXt conv2) on the fp32 vector pipe, csrc/conv_grouped.hip ----
  * `cardinality` independent 3x3 / pad 1 / stride 1 | 2 convolutions of cg = C / cardinality channels each, Cin == Cout == C,
  * cg in {4, 8, 16, 32}, cardinality >= 2, ONE dense NHWC fp32 map per launch; anything else: ERD_EUNSUPPORTED / ERD_EINVAL.
