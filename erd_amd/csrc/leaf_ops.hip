@@ -318,32 +318,34 @@ inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + pe
 
 }  // namespace
 
+// Null data pointers are legal exactly when there is nothing to do: a zero-element tensor has no storage, and the modules hand
+// zero rows through (a level without positives, an image without boxes) as the reference does.
 extern "C" int erd_qfl_rows(const float* pred, const int64_t* label, const float* score, int64_t n, int C, float* rows,
                             erd_stream_t stream) {
-    ERD_REQUIRE(pred && label && score && rows && C > 0, "qfl_rows: bad args");
+    ERD_REQUIRE(((pred && label && score && rows) || n == 0) && n >= 0 && C > 0, "qfl_rows: bad args");
     if (n > 0) hipLaunchKernelGGL(qfl_rows_kernel, dim3(blocks_for(n, 4)), dim3(256), 0, (hipStream_t)stream, pred, label, score, n, C, rows);
     return erd::check_launch("qfl_rows");
 }
 extern "C" int erd_qfl_bwd(const float* pred, const int64_t* label, const float* score, const float* coef, int64_t n, int C,
                            float* dpred, erd_stream_t stream) {
-    ERD_REQUIRE(pred && label && score && coef && dpred && C > 0, "qfl_bwd: bad args");
+    ERD_REQUIRE(((pred && label && score && coef && dpred) || n == 0) && n >= 0 && C > 0, "qfl_bwd: bad args");
     if (n > 0) hipLaunchKernelGGL(qfl_bwd_kernel, dim3(blocks_for(n * C)), dim3(256), 0, (hipStream_t)stream, pred, label, score, coef, n, C, dpred);
     return erd::check_launch("qfl_bwd");
 }
 extern "C" int erd_dfl(const float* pred, const float* target, const float* coef, int64_t m, int nb, float* rows, float* dpred,
                        erd_stream_t stream) {
-    ERD_REQUIRE(pred && target && nb >= 2 && nb <= MAXB && (rows || (dpred && coef)), "dfl: bad args");
+    ERD_REQUIRE(((pred && target && (rows || (dpred && coef))) || m == 0) && m >= 0 && nb >= 2 && nb <= MAXB, "dfl: bad args");
     if (m > 0) hipLaunchKernelGGL(dfl_kernel, dim3(blocks_for(m)), dim3(256), 0, (hipStream_t)stream, pred, target, coef, m, nb, rows, dpred);
     return erd::check_launch("dfl");
 }
 extern "C" int erd_kd_kl_rows(const float* pred, const float* soft, const float* coef, int64_t m, int nb, float T, float* rows,
                               float* dpred, erd_stream_t stream) {
-    ERD_REQUIRE(pred && soft && nb >= 2 && nb <= MAXB && T > 0.f && (rows || (dpred && coef)), "kd_kl_rows: bad args");
+    ERD_REQUIRE(((pred && soft && (rows || (dpred && coef))) || m == 0) && m >= 0 && nb >= 2 && nb <= MAXB && T > 0.f, "kd_kl_rows: bad args");
     if (m > 0) hipLaunchKernelGGL(kdkl_kernel, dim3(blocks_for(m)), dim3(256), 0, (hipStream_t)stream, pred, soft, coef, m, nb, T, rows, dpred);
     return erd::check_launch("kd_kl_rows");
 }
 extern "C" int erd_integral(const float* x, const float* dy, int64_t m, int nb, float* y, float* dx, erd_stream_t stream) {
-    ERD_REQUIRE(x && nb >= 2 && nb <= MAXB && (y || (dx && dy)), "integral: bad args");
+    ERD_REQUIRE(((x && (y || (dx && dy))) || m == 0) && m >= 0 && nb >= 2 && nb <= MAXB, "integral: bad args");
     if (m > 0) hipLaunchKernelGGL(integral_kernel, dim3(blocks_for(m)), dim3(256), 0, (hipStream_t)stream, x, dy, m, nb, y, dx);
     return erd::check_launch("integral");
 }
@@ -358,7 +360,7 @@ extern "C" int erd_bbox_overlaps(const float* b1, const float* b2, int64_t A, in
 }
 extern "C" int erd_giou(const float* pred, const float* target, const float* coef, int64_t n, float eps, float* rows, float* dpred,
                         erd_stream_t stream) {
-    ERD_REQUIRE(pred && target && (rows || (dpred && coef)), "giou: bad args");
+    ERD_REQUIRE(((pred && target && (rows || (dpred && coef))) || n == 0) && n >= 0, "giou: bad args");
     if (n > 0)
         hipLaunchKernelGGL(giou_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(pred),
                            reinterpret_cast<const float4*>(target), coef, n, eps, rows, reinterpret_cast<float4*>(dpred));
@@ -366,7 +368,7 @@ extern "C" int erd_giou(const float* pred, const float* target, const float* coe
 }
 extern "C" int erd_distance2bbox(const float* points, const float* dist, const float* dout, int64_t n, float max_h, float max_w,
                                  float* out, float* ddist, erd_stream_t stream) {
-    ERD_REQUIRE(points && dist && (out || (ddist && dout)), "distance2bbox: bad args");
+    ERD_REQUIRE(((points && dist && (out || (ddist && dout))) || n == 0) && n >= 0, "distance2bbox: bad args");
     if (n > 0 && out)
         hipLaunchKernelGGL(d2b_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float2*>(points),
                            reinterpret_cast<const float4*>(dist), n, max_h, max_w, reinterpret_cast<float4*>(out));
@@ -378,7 +380,7 @@ extern "C" int erd_distance2bbox(const float* points, const float* dist, const f
 }
 extern "C" int erd_bbox2distance(const float* points, const float* boxes, int64_t n, float max_dis, float eps, float* out,
                                  erd_stream_t stream) {
-    ERD_REQUIRE(points && boxes && out, "bbox2distance: bad args");
+    ERD_REQUIRE(((points && boxes && out) || n == 0) && n >= 0, "bbox2distance: bad args");
     if (n > 0)
         hipLaunchKernelGGL(b2d_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float2*>(points),
                            reinterpret_cast<const float4*>(boxes), n, max_dis, eps, reinterpret_cast<float4*>(out));

@@ -620,7 +620,9 @@ int erd_coco_eval(const double* dt_box, const double* dt_score, const int32_t* d
  *   erd_rows_mul                 out[i] = rows[i] * scale * weight[i]  (reduction='none' and its backward)
  *   erd_atss_result              AssignResult fields (gt_inds 0 / g+1, max_overlaps with -1e8 for unassigned priors, labels
  *                                -1 / class) of ONE image from the key workspace erd_atss_assign leaves behind
- *                                (atss_assigner.py:238-254) */
+ *                                (atss_assigner.py:238-254)
+ * Zero rows (n, m or A x G == 0) is a valid call that launches nothing, and then every data pointer may be null (a
+ * zero-element tensor has no storage); with rows to process a null data pointer is refused. */
 int erd_qfl_rows(const float* pred, const int64_t* label, const float* score, int64_t n, int C, float* rows, erd_stream_t stream);
 int erd_qfl_bwd(const float* pred, const int64_t* label, const float* score, const float* coef, int64_t n, int C, float* dpred,
                 erd_stream_t stream);
