@@ -119,6 +119,7 @@ _SIGNATURES = {
     "erd_wgrad_reduce_grouped": [P, i32, i32, i32, C.POINTER(WgradReduceGroups), i32, P],
     "erd_conv_wgrad_wino": [C.POINTER(WgradDesc), P],
     "erd_conv_wgrad_wino_ok": [C.POINTER(WgradDesc)],
+    "erd_conv_wgrad_wino_tile": [C.POINTER(WgradDesc)],
     "erd_wgrad_wino_reduce": [P, i32, i32, i32, P, i32, P],
     "erd_weight_transpose": [P, P, P, i32, i32, i32, i32, P],
     "erd_weight_transpose_bf16": [P, P, P, i32, i32, i32, i32, P],

@@ -265,10 +265,14 @@ int erd_wgrad_reduce_grouped(const float* part, int nsplit, int Cout, int K, con
  * It refuses (ERD_EINVAL, before any launch) bf16-stored maps or bf16 multiplicands, Cin or Cout that are not multiples of 128,
  * strides other than 1 and every layer that is not 3x3 / pad 1.  erd_conv_wgrad_wino_ok: 1 if the descriptor is taken (the
  * host's routing predicate), else 0.
+ * Two kernels compute the slabs, bit for bit the same: one position per workgroup over 256 x 256 channels where Cin and Cout are
+ * multiples of 256, one transform row over 128 x 128 otherwise (ERD_WGRAD_WINO_TILE=128|256 in the environment, read per call,
+ * forces either where the shape allows).  erd_conv_wgrad_wino_tile: 128 | 256, the one a launch would take now; 0: refused.
  * erd_wgrad_wino_reduce: dW[Cout][9][Cin] (+)= At (sum_s part[s]) At^T, slabs summed in order; accumulate: bit 0 = add into dW.
  * No rowscale / rowdot: only convolutions without BN coupling are routed here. */
 int erd_conv_wgrad_wino(const erd_wgrad_desc* d, erd_stream_t stream);
 int erd_conv_wgrad_wino_ok(const erd_wgrad_desc* d);
+int erd_conv_wgrad_wino_tile(const erd_wgrad_desc* d);
 int erd_wgrad_wino_reduce(const float* part, int nsplit, int Cout, int Cin, float* dW, int accumulate, erd_stream_t stream);
 
 /* ---- grouped 3x3 convolution (ResNeXt conv2) on the fp32 vector pipe, csrc/conv_grouped.hip ----
