@@ -114,6 +114,8 @@ _SIGNATURES = {
     "erd_conv_grouped_dgrad": [C.POINTER(ConvGroupedDesc), P],
     "erd_conv_grouped_wgrad": [P, P, P, i32, i32, i32, i32, i32, i32, i32, P],
     "erd_conv_grouped_wgrad_splits": [i32, i32, i32, i32, i32, i32],
+    "erd_deform_cols": [P, P, P, i32, i32, i32, i32, i32, P],
+    "erd_deform_cols_bwd": [P, P, P, P, P, i32, i32, i32, i32, i32, P],
     "erd_wgrad_reduce": [P, i32, i32, i32, P, P, P, i32, P, P],
     "erd_wgrad_reduce_rows": [P, i32, i32, i32, i32, P, i32, P],
     "erd_wgrad_reduce_grouped": [P, i32, i32, i32, C.POINTER(WgradReduceGroups), i32, P],

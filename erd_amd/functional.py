@@ -446,6 +446,73 @@ class ConvBNAct(Function):
         return dx, dW, dgamma, (dbeta if need_b else None), None, None, dres, None, None, None, None, None
 
 
+class DeformConvBNAct(Function):
+    """conv2 of a DCN bottleneck (mmcv DeformConv2dPack as resnet.py:174-197 builds it, + the block's frozen-statistics BN and ReLU):
+        offset = conv_offset(x) (3x3, C -> 18, bias, the layer's stride);  y = [relu](bn(col(x, offset) . W^T))
+    The offset convolution runs on the launch form of the head outputs (3x3 + bias, Cout not a multiple of 16: its gradients run at
+    Cp = 32 on zero-padded copies, functional.HeadConvBias); the sampling and its backward are csrc/conv_deform.hip; the contraction is
+    a 1x1 convolution over the 9 * C columns.  Backward gathers the columns again (they are not kept: DESIGN 2) and chains the two
+    gradients of x in ONE buffer: zero, the atomic scatter of the sampling, then the offset convolution's input gradient on top."""
+
+    @staticmethod
+    def forward(ctx, x, w, w_off, b_off, gamma, beta, mean, var, stride: int, relu: bool, eps: float):
+        K.RECORDED = any(ctx.needs_input_grad)      # see kernels.WINO_TRAIN_FWD
+        K._deform_mode_check("DeformConvBNAct", x)      # (before the offset convolution launches: the bf16 mode has no DCN path)
+        wk = ohwi(w)
+        scale, shift = _bn_fold_cached(gamma, beta, mean, var, eps)
+        x = x.contiguous()
+        N, H, W_, _ = x.shape
+        OH, OW = K.conv_out_size(H, 3, stride, 1), K.conv_out_size(W_, 3, stride, 1)
+        offset = torch.empty((N, OH, OW, 18), dtype=torch.float32, device=x.device)
+        K.conv_forward([x], ohwi(w_off), [offset], 3, stride, 1, shift=b_off.detach())
+        out = torch.empty((N, OH, OW, wk.shape[0]), dtype=x.dtype, device=x.device)
+        K.deform_conv3x3_forward(x, offset, wk, out, stride, scale=scale, shift=shift, relu=relu)
+        ctx.cfg = (stride, relu, eps)
+        ctx.bias_param = b_off
+        ctx.save_for_backward(x, w, w_off, mean, var, scale, out, offset)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, w_off, mean, var, scale, out, offset = ctx.saved_tensors
+        stride, relu, eps = ctx.cfg
+        need_x, need_w, need_wo, need_bo, need_g, need_b = ctx.needs_input_grad[0:6]
+        dz, dbeta = K.relu_bwd_colsum(out if relu else None, dy.contiguous(), relu, want_colsum=need_g or need_b)
+        wk = ohwi(w)
+        dW = dgamma = dWo = dbo = dx = None
+        if need_w or need_g:
+            rowdot = K.zeros_f32(scale.numel(), scale.device) if need_g else None
+            part, S = K.deform_conv3x3_wgrad_partials(x, offset, dz, stride)
+            dW = _emit_wgrad(w, part, S, wk, scale, rowdot)
+            if need_g:
+                dgamma = K.bn_dgamma(rowdot, dbeta, mean, var, eps)
+        if need_x or need_wo or need_bo:
+            dx = torch.zeros_like(x)
+            doffset = K.deform_conv3x3_dgrad(dz, wk, scale, x, offset, stride, dx)
+            # the offset convolution's gradients contract over its 18 output channels: at Cp = 32 on zero-padded copies
+            wok = ohwi(w_off)
+            Cp = 32
+            dop = K.pad_channels(doffset, Cp)
+            if need_wo:
+                part, S = K.conv_wgrad_partials([x], [dop], 3, stride, 1)
+                sink = _sink(w_off)
+                if sink is not None:
+                    K.wgrad_reduce_rows(part, S, Cp, ohwi(sink), True)
+                    _sunk(w_off)
+                else:
+                    dWk = torch.empty_like(wok)
+                    K.wgrad_reduce_rows(part, S, Cp, dWk, False)
+                    dWo = _to_oihw(dWk)
+            if need_bo:
+                dbo = _bias_grad(ctx.bias_param, doffset)
+            if need_x:
+                wp = K.pad_channels(wok.reshape(1, -1), Cp * wok[0].numel()).view(Cp, *wok.shape[1:])
+                K.conv_dgrad([dop], K.weight_transpose(wp), [dx], 3, stride, 1, accumulate=True)
+            else:
+                dx = None
+        return dx, dW, dWo, dbo, dgamma, (dbeta if need_b else None), None, None, None, None, None
+
+
 class BottleneckFn(Function):
     """A whole ResNet bottleneck (resnet.py:263-302) as ONE autograd node with a hand-scheduled backward:
         o1 = relu(bn1(conv1 x)); o2 = relu(bn2(conv2 o1)); y = relu(bn3(conv3 o2) + shortcut(x))

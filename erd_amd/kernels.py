@@ -576,6 +576,95 @@ def _conv_grouped_wgrad_partials(x: Tensor, dz: Tensor, stride: int, cardinality
     return part, S
 
 
+# ---------------------------------------------------------------------------------------------
+# deformable 3x3 convolution (DCNv1, conv2 of a Bottleneck with dcn=..., resnet.py:174-197; csrc/conv_deform.hip).  The sampling
+# kernels gather / scatter the 9 * C bilinear columns of every output pixel; the contraction with the weight [Cout, 9 * C] is a 1x1
+# convolution over those columns on the launch forms every other layer uses (forward with the scale / shift / ReLU epilogue, the 1x1
+# input-gradient form, the 1x1 weight-gradient partials + wgrad_reduce), so "f32" and "f32x3" both work and the BN fold needs nothing
+# new.  One dense NHWC fp32 map per launch.  The column buffer is a per-stream workspace: backward gathers it again.
+# ---------------------------------------------------------------------------------------------
+def _deform_mode_check(what: str, *ts) -> None:
+    if COMPUTE == "bf16" or any(t is not None and t.dtype != torch.float32 for t in ts):
+        raise NotImplementedError(f"{what}: deformable convolutions are not built for the compute mode 'bf16' "
+                                  "(--amp, maps stored as bf16); use 'f32x3' or 'f32'")
+
+
+def _deform_geometry(x: Tensor, offset: Tensor, stride: int):
+    for t in (x, offset):
+        _check_map(t)
+        assert t.is_contiguous(), "deformable convolutions take dense NHWC maps"
+    N, IH, IW, Cc = x.shape
+    OH, OW = conv_out_size(IH, 3, stride, 1), conv_out_size(IW, 3, stride, 1)
+    assert offset.shape == (N, OH, OW, 18), (tuple(x.shape), tuple(offset.shape), stride)
+    return N, IH, IW, Cc, OH, OW
+
+
+def deform_cols(x: Tensor, offset: Tensor, stride: int, out: Optional[Tensor] = None) -> Tensor:
+    """col [N, OH, OW, 9 * C] (tap-major): the bilinear samples of x [N, IH, IW, C] at the 3x3 / pad 1 taps displaced by
+    offset [N, OH, OW, 18] (channel 2t = dy, 2t + 1 = dx of tap t).  Written in full; `out` defaults to the stream's workspace."""
+    _require_gpu(x, offset)
+    _deform_mode_check("deform_cols", x, offset, out)
+    N, IH, IW, Cc, OH, OW = _deform_geometry(x, offset, stride)
+    if out is None:
+        out = ws_float("deform_col", N * OH * OW * 9 * Cc, x.device).view(N, OH, OW, 9 * Cc)
+    assert out.shape == (N, OH, OW, 9 * Cc) and out.is_contiguous()
+    npix = N * OH * OW
+    _timed_call("deform_cols", 8.0 * npix * 9 * Cc, "erd_deform_cols", _p(x), _p(offset), _p(out), N, IH, IW, Cc, stride, _stream(),
+                nbytes=4.0 * (x.numel() + offset.numel() + out.numel()) if _TIMING is not None else 0.0,
+                tag=f"px{npix} C{Cc} s{stride}" if TIMING_DETAIL else "")
+    return out
+
+
+def deform_cols_bwd(dcol: Tensor, x: Tensor, offset: Tensor, stride: int, dx: Tensor, doffset: Optional[Tensor] = None) -> Tensor:
+    """dx += the scatter of dcol [N, OH, OW, 9 * C] through the bilinear corner weights (fp32 atomics: dx ACCUMULATES onto what it
+    holds, last bits may differ from run to run); returns doffset [N, OH, OW, 18], written in full in a fixed summation order."""
+    _require_gpu(dcol, x, offset, dx)
+    _deform_mode_check("deform_cols_bwd", dcol, x, offset, dx, doffset)
+    N, IH, IW, Cc, OH, OW = _deform_geometry(x, offset, stride)
+    assert dcol.shape == (N, OH, OW, 9 * Cc) and dcol.is_contiguous() and dx.shape == x.shape and dx.is_contiguous()
+    if doffset is None:
+        doffset = torch.empty_like(offset)
+    assert doffset.shape == offset.shape and doffset.is_contiguous()
+    npix = N * OH * OW
+    _timed_call("deform_cols_bwd", 16.0 * npix * 9 * Cc, "erd_deform_cols_bwd", _p(dcol), _p(x), _p(offset), _p(dx), _p(doffset), N, IH, IW,
+                Cc, stride, _stream(), nbytes=4.0 * (5 * dcol.numel() + offset.numel()) if _TIMING is not None else 0.0,
+                tag=f"px{npix} C{Cc} s{stride}" if TIMING_DETAIL else "")
+    return doffset
+
+
+def _deform_w1x1(w: Tensor) -> Tensor:
+    """the OHWI view [Cout, 3, 3, C] of the parameter as the 1x1 weight [Cout, 1, 1, 9 * C] over the columns"""
+    assert w.is_contiguous() and w.shape[1] == 3 and w.shape[2] == 3, tuple(w.shape)
+    return w.view(w.shape[0], 1, 1, 9 * w.shape[3])
+
+
+def deform_conv3x3_forward(x: Tensor, offset: Tensor, w: Tensor, out: Tensor, stride: int, scale: Optional[Tensor] = None,
+                           shift: Optional[Tensor] = None, relu: bool = False) -> None:
+    """out = [relu](col(x, offset) . w^T * scale + shift); w is the parameter's OHWI view [Cout, 3, 3, C]"""
+    _deform_mode_check("deform_conv3x3_forward", x, offset, w, out)
+    col = deform_cols(x, offset, stride)
+    conv_forward([col], _deform_w1x1(w), [out], 1, 1, 0, scale=scale, shift=shift, relu=relu)
+
+
+def deform_conv3x3_dgrad(dz: Tensor, w: Tensor, rowscale: Optional[Tensor], x: Tensor, offset: Tensor, stride: int,
+                         dx: Tensor) -> Tensor:
+    """dcol = dz . (w * rowscale) through the 1x1 input-gradient form, then dx += its scatter; returns doffset"""
+    _deform_mode_check("deform_conv3x3_dgrad", dz, w, x, offset, dx)
+    N, OH, OW, _ = dz.shape
+    K9 = 9 * x.shape[3]
+    dcol = ws_float("deform_dcol", N * OH * OW * K9, x.device).view(N, OH, OW, K9)
+    conv_dgrad([dz], weight_transpose(_deform_w1x1(w), rowscale), [dcol], 1, 1, 0)
+    return deform_cols_bwd(dcol, x, offset, stride, dx)
+
+
+def deform_conv3x3_wgrad_partials(x: Tensor, offset: Tensor, dz: Tensor, stride: int):
+    """(part [S, Cout, 1, 9 * C], S): the 1x1 weight-gradient partial slabs over the re-gathered columns; wgrad_reduce folds them
+    against the parameter's OHWI view (K = 9 * C)"""
+    _deform_mode_check("deform_conv3x3_wgrad_partials", x, offset, dz)
+    col = deform_cols(x, offset, stride)
+    return conv_wgrad_partials([col], [dz], 1, 1, 0)
+
+
 WINOGRAD = _os.environ.get("ERD_WINO", "1") != "0"     # F(2x2,3x3) for the fp32 3x3 stride-1 convolutions (winograd.hip)
 
 

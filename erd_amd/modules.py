@@ -66,6 +66,24 @@ class ConvHolder(nn.Module):
                 self.bias.fill_(bias)
 
 
+class DeformConvHolder(nn.Module):
+    """mmcv.ops.DeformConv2dPack (DCNv1, deform_groups 1, groups 1) as resnet.py:174-197 builds conv2 of a DCN Bottleneck: `weight`
+    [planes, planes, 3, 3] (no bias) and the child `conv_offset`, a plain 3x3 convolution planes -> 18 with bias at the layer's stride,
+    ZERO at construction (DeformConv2dPack.init_offset) -- the keys `conv2.weight`, `conv2.conv_offset.{weight,bias}` of an
+    mmdet-trained dconv checkpoint."""
+
+    def __init__(self, cin: int, cout: int, stride: int = 1):
+        super().__init__()
+        self.in_channels, self.out_channels, self.k, self.stride, self.padding, self.groups = cin, cout, 3, stride, 1, 1
+        self.weight = _conv_weight(cout, cin, 3)
+        with torch.no_grad():      # mmcv's DeformConv2d.reset_parameters keeps resnet.py's kaiming_init for conv layers
+            self.weight.normal_(0, math.sqrt(2.0 / (cout * 9)))
+        self.conv_offset = ConvHolder(cin, 18, 3, stride, 1, bias=True)
+        with torch.no_grad():
+            self.conv_offset.weight.zero_()
+            self.conv_offset.bias.zero_()
+
+
 class FrozenStatBN(nn.Module):
     """BatchNorm2d parameters/buffers; statistics are never updated (norm_eval=True, resnet.py:648-657)."""
 
@@ -166,8 +184,12 @@ class Bottleneck(nn.Module):
     GROUPED_CG = (4, 8, 16, 32)      # channels per group the grouped kernels take (csrc/conv_grouped.hip)
 
     def __init__(self, inplanes: int, planes: int, stride: int, downsample: bool, bn_requires_grad: bool = True,
-                 groups: int = 1, base_width: int = 4, base_channels: int = 64):
+                 groups: int = 1, base_width: int = 4, base_channels: int = 64, dcn: Optional[dict] = None):
         super().__init__()
+        # resnet.py:174-186: with dcn, conv2 is a DeformConv2dPack -- unless fallback_on_stride keeps the plain conv2 of a stride-2 block
+        self.with_dcn = dcn is not None and not (dcn.get("fallback_on_stride", False) and stride > 1)
+        if self.with_dcn and groups != 1:
+            raise NotImplementedError(f"Bottleneck(groups={groups}, dcn={dcn!r}): grouped deformable convolutions are not built")
         # ResNeXt (resnext.py:29-33): conv1 / conv2 / conv3 run at `width`, conv2 in `groups` groups; groups = 1 is the ResNet block
         width = planes if groups == 1 else math.floor(planes * (base_width / base_channels)) * groups
         if groups > 1 and width // groups not in self.GROUPED_CG:
@@ -175,7 +197,10 @@ class Bottleneck(nn.Module):
                                       f"{width // groups} channels per group; supported: {', '.join(map(str, self.GROUPED_CG))}")
         self.conv1 = ConvHolder(inplanes, width, 1)
         self.bn1 = FrozenStatBN(width, requires_grad=bn_requires_grad)
-        self.conv2 = ConvHolder(width, width, 3, stride, 1, groups=groups)     # style='pytorch': stride on the 3x3
+        if self.with_dcn:
+            self.conv2 = DeformConvHolder(width, width, stride)
+        else:
+            self.conv2 = ConvHolder(width, width, 3, stride, 1, groups=groups)     # style='pytorch': stride on the 3x3
         self.bn2 = FrozenStatBN(width, requires_grad=bn_requires_grad)
         self.conv3 = ConvHolder(width, planes * 4, 1)
         self.bn3 = FrozenStatBN(planes * 4, requires_grad=bn_requires_grad)
@@ -200,10 +225,15 @@ class Bottleneck(nn.Module):
         return out
 
     def forward(self, x: Tensor) -> Tensor:      # NHWC map
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if not self.with_dcn and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             return Fn.BottleneckFn.apply(x, self.stride, self.bn1.eps, *self._params())
         out = self._cba(x, self.conv1, self.bn1, None, True)
-        out = self._cba(out, self.conv2, self.bn2, None, True)
+        if self.with_dcn:      # leaf nodes composed here: BottleneckFn / ResLayerFn stay the plain blocks' nodes
+            c2, b2 = self.conv2, self.bn2
+            out = Fn.DeformConvBNAct.apply(out, c2.weight, c2.conv_offset.weight, c2.conv_offset.bias, b2.weight, b2.bias,
+                                           b2.running_mean, b2.running_var, c2.stride, True, b2.eps)
+        else:
+            out = self._cba(out, self.conv2, self.bn2, None, True)
         identity = x
         if self.downsample is not None:
             identity = self._cba(x, self.downsample[0], self.downsample[1], None, False)
@@ -224,7 +254,7 @@ class ResNet(nn.Module):
         if depth not in self.arch_settings:
             raise KeyError(f"invalid depth {depth} for resnet (bottleneck depths 50/101/152 are built)")
         unsupported = dict(in_channels=(in_channels, 3), base_channels=(base_channels, 64), style=(style, "pytorch"),
-                           deep_stem=(deep_stem, False), avg_down=(avg_down, False), dcn=(dcn, None),
+                           deep_stem=(deep_stem, False), avg_down=(avg_down, False),
                            plugins=(plugins, None), conv_cfg=(conv_cfg, None), with_cp=(with_cp, False))
         for k, (v, want) in unsupported.items():
             if v != want:
@@ -233,6 +263,18 @@ class ResNet(nn.Module):
         if not norm_eval:
             raise NotImplementedError("norm_eval=False (batch statistics) is not on the ERD path "
                                       "(configs/gfl_increment/*.py:43 norm_eval=True)")
+        # resnet.py:448-481: dcn=dict(type='DCN', deform_groups=1, fallback_on_stride=...) on the stages stage_with_dcn marks
+        self.dcn, self.stage_with_dcn = (None if dcn is None else dict(dcn)), tuple(stage_with_dcn)
+        if dcn is not None:
+            assert len(self.stage_with_dcn) == num_stages, f"stage_with_dcn {stage_with_dcn!r} needs {num_stages} entries"
+            if dcn.get("type") != "DCN":
+                raise NotImplementedError(f"ResNet(dcn type={dcn.get('type')!r}): only 'DCN' (DCNv1) is built; modulated "
+                                          "deformable convolution (DCNv2) is not")
+            if dcn.get("deform_groups", 1) != 1:
+                raise NotImplementedError(f"ResNet(dcn deform_groups={dcn.get('deform_groups')!r}): only deform_groups=1 is built")
+            if self._block_kwargs().get("groups", 1) != 1:
+                raise NotImplementedError(f"{type(self).__name__}(groups={self._block_kwargs()['groups']}, dcn={dcn!r}): grouped "
+                                          "deformable convolutions (the x101-dconv rows) are not built")
         self.depth, self.num_stages, self.out_indices = depth, num_stages, tuple(out_indices)
         self.frozen_stages, self.norm_eval, self.init_cfg = frozen_stages, norm_eval, init_cfg
         bn_rg = norm_cfg.get("requires_grad", True)
@@ -244,7 +286,8 @@ class ResNet(nn.Module):
             planes = 64 * 2 ** i
             blocks = []
             for b in range(nblk):
-                blocks.append(Bottleneck(inplanes, planes, strides[i] if b == 0 else 1, b == 0, bn_rg, **self._block_kwargs()))
+                blocks.append(Bottleneck(inplanes, planes, strides[i] if b == 0 else 1, b == 0, bn_rg,
+                                         dcn=self.dcn if (self.dcn is not None and self.stage_with_dcn[i]) else None, **self._block_kwargs()))
                 inplanes = planes * 4
             name = f"layer{i + 1}"
             self.add_module(name, nn.Sequential(*blocks))
@@ -298,7 +341,9 @@ class ResNet(nn.Module):
             sd = {k[len(prefix):].lstrip("."): v for k, v in sd.items() if k.startswith(prefix)}
         sd = {k: v for k, v in sd.items() if not k.startswith("fc.")}
         own = self.state_dict()
-        missing = [k for k in own if k not in sd and not k.endswith("num_batches_tracked")]
+        # (an ImageNet file has no conv_offset: exactly those keys may be missing, and they keep their zeros -- resnet.py's
+        #  init_weights leaves DeformConv2dPack's own zero initialisation of conv_offset alone)
+        missing = [k for k in own if k not in sd and not k.endswith("num_batches_tracked") and ".conv2.conv_offset." not in k]
         unexpected = [k for k in sd if k not in own]
         if missing or unexpected:
             raise RuntimeError(f"{path}: not a ResNet-{self.depth} state dict (missing {missing[:4]}..., "
@@ -338,7 +383,7 @@ class ResNet(nn.Module):
             layer = getattr(self, name)
             ctxm = torch.no_grad() if not torch.is_grad_enabled() else torch.enable_grad()
             with ctxm:
-                if Fn.RES_LAYER_NODE and torch.is_grad_enabled() and all(
+                if Fn.RES_LAYER_NODE and torch.is_grad_enabled() and not any(blk.with_dcn for blk in layer) and all(
                         any(p.requires_grad for p in blk.parameters()) for blk in layer):
                     # the stage as ONE autograd node: its backward hands each block's dz3 straight to the block before it
                     params, counts = [], []

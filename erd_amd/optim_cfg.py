@@ -46,21 +46,28 @@ def resolve_paramwise(model: nn.Module, base_lr: float, base_wd: float, paramwis
     Per parameter with full dotted name n, own name `name` and owning module m:
       1. the keys of `custom_keys`, longest first and alphabetical among equal lengths; the first one that is a SUBSTRING of n
          sets lr = base_lr * lr_mult and weight_decay = base_wd * decay_mult (both default 1) and ends the search;
-      2. otherwise lr = base_lr * bias_lr_mult for a `bias` that does not belong to a normalisation layer, and
+      2. otherwise lr = base_lr * bias_lr_mult for a `bias` that belongs neither to a normalisation layer nor to a deformable
+         convolution (a DeformConvHolder or its `conv_offset` child), then lr = base_lr * dcn_offset_lr_mult for BOTH parameters of
+         a `conv_offset` module inside a deformable convolution (mmengine 0.7.3's rule, restated from the published source,
+         unpinned: mmengine is not a dependency), and
       3. weight_decay = base_wd * norm_decay_mult in a normalisation layer, else * bias_decay_mult for a `bias`, else
          * flat_decay_mult for a 1-D parameter; a multiplier that is not given is passed over (mmengine's `elif` chain: the
          bias of a normalisation layer takes bias_decay_mult when norm_decay_mult is absent);
-      4. dwconv_decay_mult, dcn_offset_lr_mult and bypass_duplicate have nothing to act on in these models (no depthwise or
-         deformable convolution, no shared parameter).
+      4. dwconv_decay_mult and bypass_duplicate have nothing to act on in these models (no depthwise convolution, no shared
+         parameter); dcn_offset_lr_mult acts only in models with DCN blocks (ResNet(dcn=...)).
     Frozen parameters keep the base values."""
     cfg = check_paramwise(paramwise_cfg)
     custom = cfg.get("custom_keys", {})
     keys = sorted(sorted(custom.keys()), key=len, reverse=True)
     bias_lr, bias_wd = cfg.get("bias_lr_mult"), cfg.get("bias_decay_mult")
     norm_wd, flat_wd = cfg.get("norm_decay_mult"), cfg.get("flat_decay_mult")
+    dcn_lr = cfg.get("dcn_offset_lr_mult")
+    from .modules import DeformConvHolder
+    in_dcn = {id(c) for m in model.modules() if isinstance(m, DeformConvHolder) for c in m.modules()}
     by_id: Dict[int, dict] = {}
     for prefix, m in model.named_modules():
         norm = _is_norm(m)
+        dcn = id(m) in in_dcn
         for name, p in m.named_parameters(recurse=False):
             if id(p) in by_id:
                 continue
@@ -72,8 +79,10 @@ def resolve_paramwise(model: nn.Module, base_lr: float, base_wd: float, paramwis
                     lr_mult = float(custom[key].get("lr_mult", 1.0))
                     wd_mult = float(custom[key].get("decay_mult", 1.0))
                 else:
-                    if name == "bias" and not norm and bias_lr is not None:
+                    if name == "bias" and not (norm or dcn) and bias_lr is not None:
                         lr_mult = float(bias_lr)
+                    if dcn and "conv_offset" in prefix and dcn_lr is not None:
+                        lr_mult = float(dcn_lr)
                     if norm and norm_wd is not None:
                         wd_mult = float(norm_wd)
                     elif name == "bias" and bias_wd is not None:

@@ -312,6 +312,27 @@ int erd_conv_grouped_wgrad(const float* x, const float* dz, float* part, int N, 
                            int nsplit, erd_stream_t stream);
 int erd_conv_grouped_wgrad_splits(int N, int IH, int IW, int C, int cg, int stride);
 
+/* ---- deformable convolution (DCNv1) sampling, csrc/conv_deform.hip ----
+ * mmcv.ops.DeformConv2dPack restricted to 3x3 / pad 1 / dilation 1 / deform_groups 1 / groups 1 / stride 1 | 2 (conv2 of a ResNet
+ * Bottleneck built with dcn=dict(type='DCN', deform_groups=1), resnet.py:174-197).  ONE dense NHWC fp32 map: x [N][IH][IW][C],
+ * offset [N][OH][OW][18] (channel 2t = dy, 2t + 1 = dx of tap t = 3 * kh + kw), OH = (IH - 1) / stride + 1.  Tap t of output pixel
+ * (oy, ox) samples x bilinearly at h = (float)(oy * stride - 1 + kh) + dy, w = (float)(ox * stride - 1 + kw) + dx; the sample is 0
+ * unless h > -1 && w > -1 && h < IH && w < IW (decided on the floats), and a corner outside the map contributes 0.  The operation
+ * order is stated in the source's header; the file is compiled without FMA contraction.  C % 4 == 0, stride 1 | 2, every map
+ * (col included) below 2^31 elements: otherwise ERD_EUNSUPPORTED.  All pointers 16-byte aligned.  The contraction with the weight is a
+ * 1x1 erd_conv_igemm over the 9 * C columns (kernels.deform_conv3x3_*).
+ *   erd_deform_cols      col [N][OH][OW][9][C] = the samples; written in full, the same bits under any grid / CU reserve
+ *   erd_deform_cols_bwd  dx [N][IH][IW][C] += dcol * corner weight at every in-range corner (fp32 global atomic adds, one contiguous
+ *                        run of channels of one pixel per wave-instruction: the ONE place whose last bits may differ from run to
+ *                        run; dx must not alias x); doffset [N][OH][OW][18] = the derivative w.r.t. the offsets with floor() and the
+ *                        inside test held constant (0 for an outside sample): a fixed-order reduction over C, written in full,
+ *                        the same bits under any grid / CU reserve
+ * replaces: mmcv.ops.DeformConv2dPack.forward / DeformConv2dFunction.backward (deformable im2col, col2im, col2im_coord) at the call
+ * site resnet.py:174-197, 268-300. */
+int erd_deform_cols(const float* x, const float* offset, float* col, int N, int IH, int IW, int C, int stride, erd_stream_t stream);
+int erd_deform_cols_bwd(const float* dcol, const float* x, const float* offset, float* dx, float* doffset, int N, int IH, int IW,
+                        int C, int stride, erd_stream_t stream);
+
 /* dst[ci][t'][co] = rowscale[co] * w[co][t][ci]  (t' = flip ? ntaps-1-t : t): weights of the
  * input-gradient convolution. */
 int erd_weight_transpose(const float* w, const float* rowscale, float* dst, int Cout, int ntaps,
