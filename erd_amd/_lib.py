@@ -149,6 +149,8 @@ _SIGNATURES = {
     "erd_grad_sqnorm": [P, i64, P, P],
     "erd_clip_coef": [P, i32, f32, f32, P, P],
     "erd_grad_accumulate": [P, P, i64, i32, P],
+    "erd_ema_update": [P, P, i64, f32, f32, i32, P],
+    "erd_swap_f32": [P, P, i64, P],
     "erd_ers_select": [P, P, i32, i64, i32, i32, P, P, P, P, P, P, P, P],
     "erd_grid_anchors": [P, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, i32, P],
     "erd_atss_assign": [P, P, C.POINTER(i64), i32, i64, P, P, P, i32, i32, i32, i32, P, P, P, P, P, P],

@@ -822,10 +822,69 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(float4* __restrict
     }
 }
 
+// ---- weight averaging (EMAHook) over a range of two flat buffers -----------------------------------------------------------
+// ema = fmaf(p, c, ema * d) per element -- the multiply rounded on its own, then ONE fused multiply-add: what
+// `averaged.mul_(1 - c).add_(src, alpha=c)` computes on an FMA host; c and d = 1 - c are rounded from the host's doubles.  COPY:
+// ema = p.  12 B per element (8 B copying), no reuse: an HBM pass.  Whole float4 lanes grid-stride, the n % 4 elements behind the
+// last whole lane go to the first lanes of block 0 one by one; nothing outside [0, n) is read or written.
+__device__ __forceinline__ float ema_elem(float e, float p, float c, float d) { return fmaf(p, c, __fmul_rn(e, d)); }
+
+template <bool COPY>
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t n, float c, float d) {
+    const int64_t n4 = n >> 2;
+    float4* __restrict__ e4 = reinterpret_cast<float4*>(ema);
+    const float4* __restrict__ p4 = reinterpret_cast<const float4*>(p);
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        float4 s = p4[i];
+        if (!COPY) {
+            const float4 a = e4[i];
+            s.x = ema_elem(a.x, s.x, c, d); s.y = ema_elem(a.y, s.y, c, d);
+            s.z = ema_elem(a.z, s.z, c, d); s.w = ema_elem(a.w, s.w, c, d);
+        }
+        e4[i] = s;
+    }
+    const int64_t t = n4 * 4 + threadIdx.x;
+    if (blockIdx.x == 0 && t < n) ema[t] = COPY ? p[t] : ema_elem(ema[t], p[t], c, d);
+}
+
+// a[0, n) <-> b[0, n): every element is read and written by one lane, so no third buffer and no ordering between lanes
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+    const int64_t n4 = n >> 2;
+    float4* __restrict__ a4 = reinterpret_cast<float4*>(a);
+    float4* __restrict__ b4 = reinterpret_cast<float4*>(b);
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 x = a4[i], y = b4[i];
+        a4[i] = y;
+        b4[i] = x;
+    }
+    const int64_t t = n4 * 4 + threadIdx.x;
+    if (blockIdx.x == 0 && t < n) {
+        const float x = a[t], y = b[t];
+        a[t] = y;
+        b[t] = x;
+    }
+}
+
 inline int grid_for(int64_t n, int cap = 2048) {
     int64_t b = (n + 255) / 256;
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
+
+// the grid of a streaming pass over n4 float4: one block per 256 lanes up to eight blocks per usable CU, the rest grid-strides
+// (the physical CU count is asked once: hipGetDeviceProperties is no per-launch call; the reserve is read every time)
+inline int stream_grid(int64_t n4) {
+    static int physical = 0;
+    if (physical == 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        physical = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0
+                       ? prop.multiProcessorCount : 256;
+    }
+    return grid_for(n4, 8 * erd::usable_cus(physical));
+}
+
+inline bool aligned16(const void* a, const void* b) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0; }
+inline bool disjoint(const float* a, const float* b, int64_t n) { return a + n <= b || b + n <= a; }
 
 }  // namespace
 
@@ -1356,4 +1415,26 @@ extern "C" int erd_grad_accumulate(float* acc, const float* g, int64_t n, int fi
     hipLaunchKernelGGL(grad_accumulate_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<float4*>(acc), reinterpret_cast<const float4*>(g), n / 4, first);
     return erd::check_launch("grad_accumulate");
+}
+
+// mmengine's EMAHook / ExponentialMovingAverage (mmdet ExpMomentumEMA: the coefficient is the host's) over [0, n) of two flat
+// buffers, one launch: ema = p (copy != 0) or ema = fmaf(p, c, ema * one_minus_c).  ema and p point AT the range's start,
+// 16-byte aligned; n is any count (a scalar tail behind the float4 lanes)
+extern "C" int erd_ema_update(float* ema, const float* p, int64_t n, float c, float one_minus_c, int copy, erd_stream_t stream) {
+    ERD_REQUIRE(n >= 0 && ((ema && p) || n == 0), "ema_update: bad args (null buffer or n = %lld < 0)", (long long)n);
+    if (n == 0) return 0;
+    ERD_REQUIRE(aligned16(ema, p) && disjoint(ema, p, n), "ema_update: the ranges must start on 16-byte boundaries and not overlap");
+    const dim3 grid(stream_grid(n >> 2));
+    if (copy) hipLaunchKernelGGL(ema_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, ema, p, n, c, one_minus_c);
+    else hipLaunchKernelGGL(ema_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, ema, p, n, c, one_minus_c);
+    return erd::check_launch("ema_update");
+}
+
+// a[0, n) <-> b[0, n) in one launch (parameters <-> their average around a validation pass: no third buffer of the flat size)
+extern "C" int erd_swap_f32(float* a, float* b, int64_t n, erd_stream_t stream) {
+    ERD_REQUIRE(n >= 0 && ((a && b) || n == 0), "swap_f32: bad args (null buffer or n = %lld < 0)", (long long)n);
+    if (n == 0) return 0;
+    ERD_REQUIRE(aligned16(a, b) && disjoint(a, b, n), "swap_f32: the ranges must start on 16-byte boundaries and not overlap");
+    hipLaunchKernelGGL(swap_kernel, dim3(stream_grid(n >> 2)), dim3(256), 0, (hipStream_t)stream, a, b, n);
+    return erd::check_launch("swap_f32");
 }

@@ -329,6 +329,7 @@ class _Plan(NamedTuple):
     micro_first: bool     # first micro-step of its accumulation window
     close: bool           # the step closes its window: the update is applied
     m: int                # micro-steps in the window so far
+    ema: tuple = ("skip", 0.0)    # (mode, coefficient) of the weight average after this step: "copy", "average" or "skip" (EMAHook)
 
 
 class ERDTrainer:
@@ -340,7 +341,7 @@ class ERDTrainer:
                  warmup_iters: int = 500, warmup_start_factor: float = 0.001, bucket_mb: int = 32,
                  overlap_teacher: bool = True, teacher_graph: bool = False, step_graph: bool = False,
                  paramwise_cfg: Optional[dict] = None, clip_grad: Optional[dict] = None, accumulative_counts: int = 1,
-                 optimizer: Optional[dict] = None):
+                 ema: Optional[dict] = None, optimizer: Optional[dict] = None):
         """paramwise_cfg / clip_grad / accumulative_counts: the `optim_wrapper` keys of those names (mmengine's OptimWrapper and
         DefaultOptimWrapperConstructor; optim_cfg.py).  Every update takes ONE path (_plan_step -> _update_bucket / _apply_pending
         -> _update_range); without the options it runs at their neutral values: no segment table (erd_sgd_momentum with one scalar
@@ -348,8 +349,14 @@ class ERDTrainer:
         optimizer: `optim_wrapper.optimizer`.  None or type='SGD': the SGD update from `lr`, `momentum`, `weight_decay` above.
         type='AdamW' / 'Adam' (optim_cfg.check_optimizer): lr, betas, eps and weight_decay come from THIS dict (torch's defaults
         where it is silent) and _launch_update launches erd_adam_groups instead of the SGD kernel -- same buckets, grad scale,
-        clip coefficient, accumulation window and derived-state refresh."""
+        clip coefficient, accumulation window and derived-state refresh.
+        ema: a checked EMAHook (optim_cfg.check_custom_hooks) or None.  With it one more flat buffer `ema_buf` holds the average of
+        the trainable tensors (frozen ones are the model's own under both sets of weights); every training iteration ends with
+        ONE more launch per updated range (erd_ema_update, behind the range's optimizer launch on the same stream).  What it does
+        -- copy, average with a coefficient, nothing -- is decided on the host in _plan_step from `ema_steps` (optim_cfg.ema_action),
+        like the learning rate.  swap_ema() exchanges parameters and average (validation scores the average)."""
         self.model = model
+        self.ema = None if ema is None else dict(ema)
         self.opt = OC.check_optimizer(optimizer)
         self.adam = self.opt["type"] in OC.ADAM_TYPES
         if self.adam:
@@ -387,6 +394,12 @@ class ERDTrainer:
         self.exp_avg_sq = torch.zeros_like(self.flat.momentum) if self.adam else None
         self._t = 0
         self._plan = _Plan(lr=self.base_lr, t=0, micro_first=True, close=True, m=1)
+        # EMAHook: the average (a copy until averaging starts), the averages counted so far, the epoch the runner is in
+        # (begin_epoch), and whether parameters and average are exchanged at the moment (swap_ema)
+        self.ema_buf = self.flat.data.clone() if self.ema is not None else None
+        self.ema_steps = 0
+        self.epoch = 0
+        self.ema_swapped = False
         # optim_wrapper options.  `resolved`: per-parameter lr multiplier / weight decay (model.parameters() order); `_table`: its
         # device form, one segment per flat parameter (also built for clipping alone: the coefficient enters through the same
         # kernel); `_acc`: the accumulation window's gradient sum (backward kernels need flat.grad zero at the start of every
@@ -489,7 +502,11 @@ class ERDTrainer:
         if close:
             self._window = 0
             self._t += 1
-        self._plan = _Plan(self.last_lr, self._t, micro_first, close, m)
+        act = ("skip", 0.0)
+        if self.ema is not None:
+            mode, c, self.ema_steps = OC.ema_action(self.ema, self.ema_steps, OC.ema_started(self.ema, self.iter, self.epoch))
+            act = (mode, c)
+        self._plan = _Plan(self.last_lr, self._t, micro_first, close, m, act)
         if close and self.clip is not None:
             log_vars["grad_norm"] = self._new_norm_out()[0]
 
@@ -518,6 +535,12 @@ class ERDTrainer:
             K.sgd_momentum_groups_(flat.data[s:e], g[s:e], flat.momentum[s:e], s, self._table, plan.lr, self.momentum, scale,
                                    self._first, coef)
 
+    def _launch_ema(self, s: int, e: int) -> None:
+        """EMAHook's work of the planned step over [s, e) of the flat buffers, on the current stream (behind the range's update)"""
+        mode, c = self._plan.ema
+        if mode != "skip":
+            K.ema_update(self.ema_buf[s:e], self.flat.data[s:e], c, copy=mode == "copy")
+
     def _refresh_derived(self, b: Optional[int]) -> None:
         """refreshes what the coming step reads instead of the weights of bucket b (None: of all buckets): the folded scales and
         shifts of every trainable BN of the student (one launch), then the prepared weights -- transposed weights, Winograd weight
@@ -536,6 +559,8 @@ class ERDTrainer:
         prepared weights"""
         s, e = (0, self.flat.total) if b is None else self.flat.buckets[b][:2]
         self._launch_update(s, e)
+        if self.ema is not None:
+            self._launch_ema(s, e)
         self.flat.refresh_shadow(b)
         self._refresh_derived(b)
 
@@ -584,6 +609,8 @@ class ERDTrainer:
                 self._apply_window()
         if self._plan.close:
             self._first = False
+        elif self.ema is not None:           # a micro-step inside its window: the hook runs all the same, on unchanged parameters;
+            self._launch_ema(0, self.flat.total)     # the current stream owns them now (the update stream has been joined)
         self._pending = False
 
     def flush(self, close_window: bool = True) -> None:
@@ -592,7 +619,9 @@ class ERDTrainer:
         self._apply_pending()
         if close_window and self._window > 0:
             self._t += 1
-            self._plan = self._plan._replace(t=self._t, close=True, m=self._window)
+            # (this update belongs to no iteration: the hook does not run, but an average that is still a copy stays one)
+            self._plan = self._plan._replace(t=self._t, close=True, m=self._window,
+                                             ema=("copy" if self.ema is not None and self.ema_steps == 0 else "skip", 0.0))
             self._window = 0
             if self.clip is not None:
                 self._new_norm_out()
@@ -630,6 +659,38 @@ class ERDTrainer:
         self.cu_reserve = int(candidates[best])
         return {"cu_reserve": self.cu_reserve, "probed": True, "candidates": [int(c) for c in candidates],
                 "local_seconds_per_step": [round(t / max(steps, 1), 5) for t in secs], "steps_per_candidate": steps}
+
+    def swap_ema(self) -> None:
+        """exchange parameters and average in place (one launch over the flat buffers, no third buffer) and let everything derived
+        from the parameters follow, as after an update: bf16 shadows, BN folds, prepared weights; captured steps are recorded
+        anew.  Call it twice around whatever should see the averaged weights (Runner.validate)."""
+        if self.ema is None:
+            raise RuntimeError("swap_ema: this trainer has no average (custom_hooks EMAHook)")
+        self.flush()
+        K.swap_(self.flat.data, self.ema_buf)
+        self.ema_swapped = not self.ema_swapped
+        self.flat.refresh_shadow()
+        self._refresh_derived(None)
+        self._drop_step_graphs()
+
+    def ema_state(self) -> dict:
+        """`steps` and device copies of (parameters, average) per trainable tensor name, after flush(): what a checkpoint is
+        written from (the live model is not touched)"""
+        self.flush()
+        raw, avg = (self.ema_buf, self.flat.data) if self.ema_swapped else (self.flat.data, self.ema_buf)
+        out = {}
+        for name, p, off in zip(self.flat.names, self.flat.params, self.flat.offsets):
+            out[name] = (_storage_view(raw, off, p).detach().clone(), _storage_view(avg, off, p).detach().clone())
+        return dict(steps=self.ema_steps, tensors=out)
+
+    def load_ema_state(self, steps: int, averaged: Optional[Dict[str, Tensor]]) -> None:
+        """restore the average (name -> tensor, None / a missing name: a copy of the parameter as it stands) and its count"""
+        self.flush()
+        self.ema_buf.copy_(self.flat.data)
+        for name, p, off in zip(self.flat.names, self.flat.params, self.flat.offsets):
+            if averaged is not None and name in averaged:
+                _storage_view(self.ema_buf, off, p).copy_(averaged[name].to(self.device))
+        self.ema_steps = int(steps)
 
     def join_streams(self) -> None:
         """order every stream the trainer launches on (teacher side stream, tower / trailing weight-gradient streams, the update
@@ -836,6 +897,8 @@ class ERDTrainer:
         parameter this step updates).  The following call must pass that same `inputs` object to pick the result up."""
         model = self.model
         cur = torch.cuda.current_stream(self.device)
+        if self.ema_swapped:
+            raise RuntimeError("train_step while parameters and average are exchanged: swap_ema() them back first")
         if self.step_graph:
             self._apply_pending()            # the SGD update of the previous step: one eager launch (its learning rate is a host value)
             log_vars = self._train_step_graph(inputs, data_samples)

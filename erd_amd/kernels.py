@@ -1702,6 +1702,27 @@ def grad_accumulate_(acc: Tensor, g: Tensor, first: bool) -> None:
     call("erd_grad_accumulate", _p(acc), _p(g), acc.numel(), 1 if first else 0, _stream())
 
 
+def _check_flat_pair(a: Tensor, b: Tensor) -> None:
+    _require_gpu(a, b)
+    assert a.dtype == torch.float32 and b.dtype == torch.float32, "fp32 ranges"
+    assert a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel() and a.device == b.device
+
+
+def ema_update(ema: Tensor, p: Tensor, c: float, copy: bool = False) -> None:
+    """EMAHook's average over two equally long fp32 ranges, one launch: ema = p (copy), else ema = fmaf(p, c32, ema * d32) with
+    c32 = float(c) and d32 = float(1 - c), each rounded once from the double HERE (as adam_groups_ does for its betas: ctypes
+    rounds a Python float to the c_float argument)"""
+    _check_flat_pair(ema, p)
+    c = float(c)
+    call("erd_ema_update", _p(ema), _p(p), ema.numel(), c, 1.0 - c, 1 if copy else 0, _stream())
+
+
+def swap_(a: Tensor, b: Tensor) -> None:
+    """a <-> b over two equally long fp32 ranges, one launch, no third buffer"""
+    _check_flat_pair(a, b)
+    call("erd_swap_f32", _p(a), _p(b), a.numel(), _stream())
+
+
 # ---------------------------------------------------------------------------------------------
 # ERS / anchors / ATSS / losses
 # ---------------------------------------------------------------------------------------------

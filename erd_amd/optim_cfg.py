@@ -199,3 +199,93 @@ def adam_param_group(optimizer: dict, lr: float, initial_lr: float, weight_decay
     return dict(lr=lr, betas=tuple(optimizer["betas"]), eps=optimizer["eps"], weight_decay=weight_decay, amsgrad=False,
                 maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
                 decoupled_weight_decay=optimizer["type"] == "AdamW", initial_lr=initial_lr, params=list(params))
+
+
+# ---- custom_hooks: EMAHook (weight averaging) ------------------------------------------------------------------------------------
+# mmengine's EMAHook / ExponentialMovingAverage restated from their documented behaviour (NOT pinned against mmengine, DESIGN.md
+# section 8.9); the one formula the reference tree holds is mmdet's ExpMomentumEMA.avg_func (mmdet/models/layers/ema.py:53-66).
+EMA_TYPES = ("ExponentialMovingAverage", "ExpMomentumEMA")
+EMA_HOOK_KEYS = ("type", "ema_type", "strict_load", "begin_iter", "begin_epoch", "priority")
+EMA_MODEL_KEYS = ("momentum", "interval", "update_buffers", "device")
+
+
+def check_custom_hooks(custom_hooks) -> Optional[dict]:
+    """`custom_hooks` -> None (absent or empty) or the checked EMAHook: dict(ema_type, momentum, gamma, interval, begin_iter,
+    begin_epoch, update_buffers, strict_load).  EMAHook is the one hook type built; `priority` is accepted and ignored (the
+    average is taken after the iteration's update, nothing else competes for the slot); `update_buffers` is accepted with either
+    value and changes nothing (frozen tensors and BN statistics are not averaged); `strict_load` is accepted and
+    has nothing to act on (a resumed average takes the keys the checkpoint holds, a missing one starts as a copy of its
+    parameter).  Everything else raises ValueError naming the key."""
+    if custom_hooks is None:
+        return None
+    if not isinstance(custom_hooks, (list, tuple)):
+        raise ValueError(f"custom_hooks must be a list of dicts, got {type(custom_hooks).__name__}")
+    if len(custom_hooks) == 0:
+        return None
+    hooks = [dict(h.to_dict() if hasattr(h, "to_dict") else h) for h in custom_hooks]
+    for h in hooks:
+        if h.get("type") != "EMAHook":
+            raise ValueError(f"custom_hooks: type={h.get('type')!r} is not built (built: EMAHook)")
+    if len(hooks) > 1:
+        raise ValueError("custom_hooks: more than one 'EMAHook' entry (one average per model is built)")
+    h = hooks[0]
+    kind = h.get("ema_type", "ExponentialMovingAverage")
+    if kind not in EMA_TYPES:
+        raise ValueError(f"EMAHook: ema_type={kind!r} is not built (built: {', '.join(EMA_TYPES)})")
+    known = EMA_HOOK_KEYS + EMA_MODEL_KEYS + (("gamma",) if kind == "ExpMomentumEMA" else ())
+    for k in h:
+        if k not in known:
+            raise ValueError(f"EMAHook: unknown key '{k}' for {kind} (known: {', '.join(known)})")
+    if h.get("device") is not None:
+        raise ValueError(f"EMAHook: device={h['device']!r} is not built (the average lives beside the parameters)")
+    momentum = float(h.get("momentum", 0.0002))
+    if not 0.0 < momentum < 1.0:
+        raise ValueError(f"EMAHook: momentum={momentum} must lie in (0, 1)")
+    gamma = h.get("gamma", 2000)
+    if not float(gamma) > 0:
+        raise ValueError(f"EMAHook: gamma={gamma!r} must be positive")
+    interval = h.get("interval", 1)
+    if int(interval) != interval or int(interval) < 1:
+        raise ValueError(f"EMAHook: interval={interval!r} must be a positive integer")
+    begin = {}
+    for k in ("begin_iter", "begin_epoch"):
+        v = h.get(k, 0)
+        if int(v) != v or int(v) < 0:
+            raise ValueError(f"EMAHook: {k}={v!r} must be a non-negative integer")
+        begin[k] = int(v)
+    if begin["begin_iter"] > 0 and begin["begin_epoch"] > 0:
+        raise ValueError("EMAHook: begin_iter and begin_epoch are both set (give one of them)")
+    return dict(ema_type=kind, momentum=momentum, gamma=float(gamma), interval=int(interval), update_buffers=bool(h.get("update_buffers", False)),
+                strict_load=bool(h.get("strict_load", False)), **begin)
+
+
+def ema_coefficient(kind: str, momentum: float, gamma: float, steps: int) -> float:
+    """the weight of the parameters in the average taken when `steps` averages have been counted, a double:
+    ExponentialMovingAverage: momentum; ExpMomentumEMA: (1 - momentum) * exp(-(1 + steps) / gamma) + momentum (ema.py:64-65)"""
+    import math
+    if kind == "ExponentialMovingAverage":
+        return float(momentum)
+    if kind == "ExpMomentumEMA":
+        return (1 - momentum) * math.exp(-float(1 + steps) / gamma) + momentum
+    raise ValueError(f"ema_coefficient: ema_type={kind!r} is not built (built: {', '.join(EMA_TYPES)})")
+
+
+def ema_started(ema: dict, it: int, epoch: int) -> bool:
+    """has averaging begun at 0-based iteration `it` of 0-based epoch `epoch`?  By epoch when begin_epoch is given (> 0),
+    otherwise by iteration"""
+    if ema["begin_epoch"] > 0:
+        return epoch + 1 >= ema["begin_epoch"]
+    return it + 1 >= ema["begin_iter"]
+
+
+def ema_action(ema: dict, steps: int, started: bool) -> tuple:
+    """what EMAHook does after one training iteration -> (mode, coefficient, steps afterwards).  Not started: the average is a
+    copy of the parameters and `steps` stays 0.  Started: the first call copies, later ones average when steps % interval == 0
+    and otherwise leave the average alone; each of them counts."""
+    if not started:
+        return "copy", 0.0, steps
+    if steps == 0:
+        return "copy", 0.0, 1
+    if steps % ema["interval"] == 0:
+        return "average", ema_coefficient(ema["ema_type"], ema["momentum"], ema["gamma"], steps), steps + 1
+    return "skip", 0.0, steps + 1

@@ -21,7 +21,7 @@ import torch.distributed as dist
 
 from .config import Config
 from .engine import ERDTrainer
-from .optim_cfg import check_optimizer
+from .optim_cfg import check_custom_hooks, check_optimizer
 from .registry import MODELS
 from .structures import DetDataSample, InstanceData
 from .validation import val_due
@@ -47,6 +47,22 @@ def save_checkpoint(path: str, model: torch.nn.Module, trainer: Optional[ERDTrai
         trainer.flush()        # the SGD update of the last step is deferred behind the next teacher forward: apply it
                                # BEFORE the weights are read, or the file pairs stale weights with newer momentum
     ckpt = dict(meta=dict(meta or {}), state_dict=model_state_dict(model, with_teacher))
+    if trainer is not None and trainer.ema is not None:
+        # the way mmengine's EMAHook leaves a checkpoint: `state_dict` holds the AVERAGED weights (tools/test.py and the next
+        # phase's ori_checkpoint_file read the average as they stand), `ema_state_dict` the count and the raw training weights
+        # under `module.<key>` for every key outside the teacher copy.  Written from device copies: the live model is not swapped
+        host = lambda t: t.to("cpu").contiguous(memory_format=torch.contiguous_format)
+        st = trainer.ema_state()
+        missing = [k for k in st["tensors"] if k not in ckpt["state_dict"]]
+        if missing:
+            raise KeyError(f"averaged tensors without a state_dict key of their name: {missing[:4]}")
+        ema_sd = OrderedDict(steps=torch.tensor(st["steps"], dtype=torch.long))
+        for k, v in ckpt["state_dict"].items():
+            if not k.startswith("ori_model."):
+                ema_sd["module." + k] = host(st["tensors"][k][0]) if k in st["tensors"] else v.clone()
+        for k, (_, avg) in st["tensors"].items():
+            ckpt["state_dict"][k] = host(avg)
+        ckpt["ema_state_dict"] = ema_sd
     if trainer is not None:
         ckpt["optimizer"] = trainer.optimizer_state_dict()
         ckpt["meta"].update(iter=trainer.iter)
@@ -56,11 +72,24 @@ def save_checkpoint(path: str, model: torch.nn.Module, trainer: Optional[ERDTrai
     os.replace(tmp, path)
 
 
-def load_checkpoint(path: str, model: torch.nn.Module, trainer: Optional[ERDTrainer] = None, strict: bool = True) -> dict:
+def load_checkpoint(path: str, model: torch.nn.Module, trainer: Optional[ERDTrainer] = None, strict: bool = True,
+                    log: Optional[Callable[[str], None]] = None) -> dict:
+    """trainer given: a RESUME -- optimizer state and iteration are restored, and a checkpoint written under an EMAHook is
+    exchanged back (the model gets `ema_state_dict`'s raw weights, the trainer's average `state_dict`'s, `steps` is restored).
+    Without a trainer `state_dict` is loaded as it stands (under an EMAHook: the average)."""
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
     sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
     if sd and next(iter(sd)).startswith("module."):
         sd = OrderedDict((k[7:], v) for k, v in sd.items())
+    ema_sd = ckpt.get("ema_state_dict") if "state_dict" in ckpt else None
+    averaged = None
+    if trainer is not None and ema_sd is not None:
+        raw = OrderedDict((k[7:], v) for k, v in ema_sd.items() if k.startswith("module."))
+        averaged = {k: sd[k] for k in raw if k in sd}
+        sd = OrderedDict(sd)
+        sd.update(raw)
+        if trainer.ema is None and log is not None:      # never train on the average silently
+            log(f"{path} holds ema_state_dict and the config has no EMAHook: the raw weights were restored, the average was dropped")
     own = model.state_dict()
     if not any(k.startswith("ori_model.") for k in sd):      # saved without the teacher copy: keep ours
         sd = OrderedDict(sd)
@@ -71,6 +100,13 @@ def load_checkpoint(path: str, model: torch.nn.Module, trainer: Optional[ERDTrai
     if trainer is not None and "optimizer" in ckpt:
         trainer.load_optimizer_state_dict(ckpt["optimizer"])
         trainer.iter = int(ckpt.get("meta", {}).get("iter", 0))
+    if trainer is not None and trainer.ema is not None:
+        if ema_sd is not None:
+            trainer.load_ema_state(int(ema_sd["steps"]), averaged)
+        else:
+            trainer.load_ema_state(0, None)
+            if log is not None:
+                log(f"{path} holds no ema_state_dict: the average starts as a copy of the loaded weights")
     return ckpt.get("meta", {})
 
 
@@ -254,6 +290,10 @@ class Runner:
                  for k in ("paramwise_cfg", "clip_grad", "accumulative_counts") if ow.get(k) is not None}
         if checked["type"] != "SGD":
             extra["optimizer"] = checked
+        # custom_hooks: EMAHook is the one hook built, anything else raises (optim_cfg.check_custom_hooks); none: nothing changes
+        self.ema = check_custom_hooks(cfg.get("custom_hooks"))
+        if self.ema is not None:
+            extra["ema"] = self.ema
         self.trainer = ERDTrainer(self.model, lr=opt.lr if checked["type"] == "SGD" else checked["lr"], momentum=opt.get("momentum", 0.0),
                                   weight_decay=opt.get("weight_decay", 0.0),
                                   base_batch_size=asl.get("base_batch_size", 16), batch_size_per_gpu=bs,
@@ -287,9 +327,11 @@ class Runner:
             if os.path.isfile(last):
                 load_from = open(last).read().strip()
         if load_from:
-            meta = load_checkpoint(load_from, self.model, self.trainer if resume else None)
+            meta = load_checkpoint(load_from, self.model, self.trainer if resume else None, log=self.log)
             if resume:
                 self.epoch = int(meta.get("epoch", 0))
+            elif self.ema is not None:
+                self.trainer.load_ema_state(0, None)          # the average starts as a copy of what was loaded
             self.log(f"{'resumed' if resume else 'loaded'} {load_from} (epoch {self.epoch}, iter {self.trainer.iter})")
 
     @classmethod
@@ -306,6 +348,7 @@ class Runner:
             if hasattr(self.data, "set_epoch"):
                 self.data.set_epoch(self.epoch)
             self.trainer.epoch_factor = self.schedule.epoch_factor(self.epoch)
+            self.trainer.epoch = self.epoch                   # (EMAHook begin_epoch)
             t0 = time.perf_counter()
             for i, (out, nxt) in enumerate(_with_next(self.data, lambda b: b if b.get("preprocessed") else pre(b, True))):
                 # one batch of look-ahead: the trainer queues the frozen teacher's half of the following step next to this
@@ -359,14 +402,22 @@ class Runner:
 
     def validate(self) -> Dict[str, float]:
         """one validation pass of the live student on the weights after the epoch's last update (those epoch_{e}.pth holds):
-        the deferred update is applied and every stream drained first; the pass reads the trainer's state and changes none of it"""
+        the deferred update is applied and every stream drained first; the pass reads the trainer's state and changes none of it.
+        Under an EMAHook parameters and average are exchanged around the pass: it scores the averaged weights, training goes on
+        with the raw ones"""
         if self.validator is None:
             raise RuntimeError("this runner has no validation (val_cfg / val_dataloader / val_evaluator or its file is missing)")
         self.trainer.flush()
-        torch.cuda.synchronize(self.device)                   # teacher look-ahead stream, per-bucket update stream
-        t0 = time.perf_counter()
-        stats = self.validator.run(self.model)
-        torch.cuda.synchronize(self.device)
+        if self.ema is not None:
+            self.trainer.swap_ema()
+        try:
+            torch.cuda.synchronize(self.device)               # teacher look-ahead stream, per-bucket update stream
+            t0 = time.perf_counter()
+            stats = self.validator.run(self.model)
+            torch.cuda.synchronize(self.device)
+        finally:
+            if self.ema is not None:
+                self.trainer.swap_ema()
         for line in self.validator.format(self.epoch, stats):
             self.log(line)
         rec = dict(mode="val", epoch=self.epoch, time=time.perf_counter() - t0, **{f"coco/{k}": v for k, v in stats.items()})

@@ -510,6 +510,18 @@ int erd_grad_sqnorm(const float* g, int64_t n, double* partials, erd_stream_t st
 int erd_clip_coef(const double* partials, int nslots, float grad_scale, float max_norm, float* out, erd_stream_t stream);
 /* accumulative_counts: acc[0, n) = g (first != 0) or acc += g, plain fp32 adds */
 int erd_grad_accumulate(float* acc, const float* g, int64_t n, int first, erd_stream_t stream);
+/* Weight averaging (mmengine EMAHook; the coefficient of ExponentialMovingAverage / mmdet's ExpMomentumEMA, layers/ema.py:64-66,
+ * is a host double) over [0, n) of two flat fp32 buffers, one launch; ema and p point AT the range's start.
+ *   copy != 0: ema = p (c and one_minus_c are not read).
+ *   copy == 0: ema = fmaf(p, c, ema * one_minus_c): the multiply is rounded on its own, then one fused multiply-add -- what
+ *   averaged.mul_(1 - c).add_(src, alpha=c) computes on an FMA host.  c and one_minus_c = 1 - c are each rounded to fp32 once,
+ *   from the caller's double (1 - float(c) is not float(1 - c)).
+ * Both pointers on 16-byte boundaries, the ranges disjoint; n is any count (16-byte lanes and a scalar tail).  n == 0 launches
+ * nothing and returns 0; a null pointer with n > 0, n < 0, a misaligned or overlapping range return ERD_EINVAL before anything
+ * is launched.  Nothing outside [0, n) is read or written; the result does not depend on the grid (erd_set_cu_reserve). */
+int erd_ema_update(float* ema, const float* p, int64_t n, float c, float one_minus_c, int copy, erd_stream_t stream);
+/* a[0, n) <-> b[0, n), one launch, no third buffer; the argument rules of erd_ema_update. */
+int erd_swap_f32(float* a, float* b, int64_t n, erd_stream_t stream);
 
 /* ---- ERS (gfl_increment_erd.py:143-163) -------------------------------------------------------- */
 /* per image: m_c = max_k sigmoid(cls[a,k]), keep iff m_c > mean + 2*std (unbiased); m_b = max_j
