@@ -331,6 +331,28 @@ __global__ void __launch_bounds__(256) bn_dgamma_kernel(const float* __restrict_
 // ------------------------------------------------------------------------------------------------
 constexpr int GN_ROWS = 128;       // rows per block of the streaming (apply) kernels
 constexpr int GN_STAT_ROWS = 512;  // rows per block of the statistics kernels (fewer atomics per byte)
+// Rows each thread of a streaming kernel has in flight per tensor.  One 16-byte load per thread and tensor is ~11 KB per CU on the
+// head's maps (712 workgroups on 256 CUs), which holds 3.8 TB/s; four are ~45 KB per CU, past the 20-40 KB that the copy rate needs
+// at 0.75-1.5 us of loaded latency.  The apply kernels' 4 row lanes cover 16 rows per unrolled pass, eight passes per 128-row chunk,
+// and the head's launch keeps 11 waves per CU.
+constexpr int GN_FLIGHT = 4;
+// The loads of an unrolled pass as the registers they fill (four floats, or four bf16 in two dwords), all handed through ONE empty asm
+// statement before the first is used: left alone, the optimizer sinks each load to its first use and the scheduler then keeps one or
+// two in flight to save registers (a scheduling fence does not stop the first).  No instruction of its own; the values are untouched.
+typedef float raw_f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned raw_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ raw_f32x4 ld4_raw(const float* p) { return *reinterpret_cast<const raw_f32x4*>(p); }
+__device__ __forceinline__ raw_u32x2 ld4_raw(const erd::bf16s* p) { return *reinterpret_cast<const raw_u32x2*>(p); }
+__device__ __forceinline__ float4 cooked(raw_f32x4 v) { return make_float4(v.x, v.y, v.z, v.w); }
+__device__ __forceinline__ float4 cooked(raw_u32x2 v) { return erd::unpack4_bf16(make_uint2(v.x, v.y)); }
+template <typename R>
+__device__ __forceinline__ void loads_first(R (&a)[4]) {
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]));
+}
+template <typename R>
+__device__ __forceinline__ void loads_first(R (&a)[4], R (&b)[4]) {
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
+}
 
 __device__ __forceinline__ int find_level(const erd_levels& lv, int64_t a) {
     int s = 0;
@@ -429,16 +451,33 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ c, 
     const float2 mr = *reinterpret_cast<const float2*>(mean_rstd + (((int64_t)n * lv.nseg + s) * G + g) * 2);
     const float4 ga = reinterpret_cast<const float4*>(gamma)[c4];
     const float4 be = reinterpret_cast<const float4*>(beta)[c4];
-    for (int64_t r = r0 + rl; r < r1; r += 4) {
+#define GN_ROW(V, OFF)                                                     \
+        {                                                                  \
+            const float4 v = V;                                            \
+            float4 o;                                                      \
+            o.x = fmaxf((v.x - mr.x) * mr.y * ga.x + be.x, 0.f);           \
+            o.y = fmaxf((v.y - mr.x) * mr.y * ga.y + be.y, 0.f);           \
+            o.z = fmaxf((v.z - mr.x) * mr.y * ga.z + be.z, 0.f);           \
+            o.w = fmaxf((v.w - mr.x) * mr.y * ga.w + be.w, 0.f);           \
+            erd::st4(y + (OFF), o);                                        \
+        }
+    int64_t r = r0 + rl;
+#pragma unroll 1
+    for (; r + 4 * (GN_FLIGHT - 1) < r1; r += 4 * GN_FLIGHT) {      // GN_FLIGHT rows in flight per thread
         const int64_t off = ((int64_t)n * A + r) * C + c4 * 4;
-        const float4 v = erd::ld4(c + off);
-        float4 o;
-        o.x = fmaxf((v.x - mr.x) * mr.y * ga.x + be.x, 0.f);
-        o.y = fmaxf((v.y - mr.x) * mr.y * ga.y + be.y, 0.f);
-        o.z = fmaxf((v.z - mr.x) * mr.y * ga.z + be.z, 0.f);
-        o.w = fmaxf((v.w - mr.x) * mr.y * ga.w + be.w, 0.f);
-        erd::st4(y + off, o);
+        decltype(ld4_raw(c)) vv[GN_FLIGHT];
+#pragma unroll
+        for (int q = 0; q < GN_FLIGHT; ++q) vv[q] = ld4_raw(c + off + (int64_t)q * 4 * C);
+        loads_first(vv);
+#pragma unroll
+        for (int q = 0; q < GN_FLIGHT; ++q) GN_ROW(cooked(vv[q]), off + (int64_t)q * 4 * C)
     }
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    for (; r < r1; r += 4) {
+        const int64_t off = ((int64_t)n * A + r) * C + c4 * 4;
+        GN_ROW(erd::ld4(c + off), off)
+    }
+#undef GN_ROW
 }
 
 // backward pass 1: per (n,level,group) s1 = sum dyh, s2 = sum dyh*xhat (dyh = dy*mask*gamma);
@@ -457,6 +496,7 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const T* __restrict__
     const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;  // 16 columns x 16 row lanes (see gn_stats_kernel)
     const int c4 = blockIdx.z * 16 + cl;
     const int g = c4 >> 1;
+    static_assert(GN_FLIGHT == 4, "the unrolled loop below steps 4 x 16 rows");
     const float2 mr = *reinterpret_cast<const float2*>(mean_rstd + (((int64_t)n * lv.nseg + s) * G + g) * 2);
     const float4 ga = reinterpret_cast<const float4*>(gamma)[c4];
     const float4 be = reinterpret_cast<const float4*>(beta)[c4];
@@ -468,11 +508,32 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const T* __restrict__
             const float dm = (xh * ga.F + be.F > 0.f) ? d.F : 0.f;         \
             dg.F += dm * xh;                                               \
             db.F += dm;                                                    \
-            const float dh = dm * ga.F;                                    \
-            s1 += dh;                                                      \
-            s2 += dh * xh;                                                 \
+            {   /* the group sums feed dc: no product fused into them */   \
+                _Pragma("clang fp contract(off)")                          \
+                const float dh = dm * ga.F;                                \
+                s1 += dh;                                                  \
+                s2 += dh * xh;                                             \
+            }                                                              \
         }
+    // (s1 and s2 reach dc through the group sums.  The fp32 instantiation's two-row loop always compiled them as rounded products and
+    // plain additions; left to the compiler, the four-row loop fuses one row's dm * gamma into s1 and its dh * xh into s2, and dc
+    // moves in the last bit.  So both are spelled unfused, for every loop.)
     int64_t r = r0 + rl;
+    // four rows of both tensors in flight per thread, then two, then one: every lane adds its rows in the order r, r + 16, ... whatever
+    // the step, so s1, s2, dg and db are the sums they were
+#pragma unroll 1
+    for (; r + 48 < r1; r += 64) {
+        const int64_t off = ((int64_t)n * A + r) * C + c4 * 4;
+        decltype(ld4_raw(c)) vv[GN_FLIGHT], dd[GN_FLIGHT];
+#pragma unroll
+        for (int q = 0; q < GN_FLIGHT; ++q) {
+            vv[q] = ld4_raw(c + off + (int64_t)q * 16 * C);
+            dd[q] = ld4_raw(dy + off + (int64_t)q * 16 * C);
+        }
+        loads_first(vv, dd);
+#pragma unroll
+        for (int q = 0; q < GN_FLIGHT; ++q) { const float4 v = cooked(vv[q]), d = cooked(dd[q]); GN_ONE(x) GN_ONE(y) GN_ONE(z) GN_ONE(w) }
+    }
     for (; r + 16 < r1; r += 32) {          // two rows in flight per thread
         const int64_t off0 = ((int64_t)n * A + r) * C + c4 * 4, off1 = off0 + (int64_t)16 * C;
         const float4 v0 = erd::ld4(c + off0), d0 = erd::ld4(dy + off0);
@@ -491,10 +552,15 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const T* __restrict__
     s2 += __shfl_xor(s2, 1, 64);
     __shared__ float red[16][8][2];
     __shared__ float4 redc[16][16][2];
+    __shared__ __attribute__((aligned(16))) float outc[2][64];
     if ((cl & 1) == 0) { red[rl][cl >> 1][0] = s1; red[rl][cl >> 1][1] = s2; }
     redc[rl][cl][0] = dg;
     redc[rl][cl][1] = db;
     __syncthreads();
+#ifdef ERD_GN_BWD_NOATOMICS     // timing probe (tools/build_probe.sh): what the 16 double and 128 float atomics of a workgroup cost -- only a
+                                // workgroup whose first sum is a value no data gives issues them (results are wrong)
+    if (red[0][0][0] != -1.2345e33f) return;
+#endif
     if (threadIdx.x < 16) {
         const int gg = threadIdx.x >> 1, k = threadIdx.x & 1;
         double t = 0.0;
@@ -509,12 +575,13 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const T* __restrict__
             a.x += redc[q][cc][0].x; a.y += redc[q][cc][0].y; a.z += redc[q][cc][0].z; a.w += redc[q][cc][0].w;
             b.x += redc[q][cc][1].x; b.y += redc[q][cc][1].y; b.z += redc[q][cc][1].z; b.w += redc[q][cc][1].w;
         }
-        const int ch0 = (blockIdx.z * 16 + cc) * 4;
-        atomicAdd(dgamma + ch0 + 0, a.x); atomicAdd(dgamma + ch0 + 1, a.y);
-        atomicAdd(dgamma + ch0 + 2, a.z); atomicAdd(dgamma + ch0 + 3, a.w);
-        atomicAdd(dbeta + ch0 + 0, b.x); atomicAdd(dbeta + ch0 + 1, b.y);
-        atomicAdd(dbeta + ch0 + 2, b.z); atomicAdd(dbeta + ch0 + 3, b.w);
+        *reinterpret_cast<float4*>(&outc[0][cc * 4]) = a;
+        *reinterpret_cast<float4*>(&outc[1][cc * 4]) = b;
     }
+    // the workgroup's 64 dgamma and 64 dbeta shares as two wave-wide adds of 256 contiguous bytes each (one lane per channel), not eight
+    // of 16 lanes at a 16-byte stride: the same sums in a quarter of the 64-byte atomic requests, all of which queue on 2 KB of addresses
+    __syncthreads();
+    if (threadIdx.x < 128) atomicAdd((threadIdx.x < 64 ? dgamma : dbeta) + blockIdx.z * 64 + (threadIdx.x & 63), outc[threadIdx.x >> 6][threadIdx.x & 63]);
 }
 
 // backward pass 2: dc = rstd * (dyh - (s1 + xhat*s2)/m)
@@ -536,21 +603,40 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
     const float m1 = (float)stats[si * 2] * inv_m, m2 = (float)stats[si * 2 + 1] * inv_m;
     const float4 ga = reinterpret_cast<const float4*>(gamma)[c4];
     const float4 be = reinterpret_cast<const float4*>(beta)[c4];
-    for (int64_t r = r0 + rl; r < r1; r += 4) {
-        const int64_t off = ((int64_t)n * A + r) * C + c4 * 4;
-        const float4 v = erd::ld4(c + off);
-        const float4 d = erd::ld4(dy + off);
-        float4 o;
 #define GN_ONE(F)                                                          \
         {                                                                  \
             const float xh = (v.F - mr.x) * mr.y;                          \
             const float dh = (xh * ga.F + be.F > 0.f) ? d.F * ga.F : 0.f;  \
             o.F = mr.y * (dh - m1 - xh * m2);                              \
         }
-        GN_ONE(x) GN_ONE(y) GN_ONE(z) GN_ONE(w)
-#undef GN_ONE
-        erd::st4(dc + off, o);
+#define GN_ROW(V, D, OFF)                                                  \
+        {                                                                  \
+            const float4 v = V, d = D;                                     \
+            float4 o;                                                      \
+            GN_ONE(x) GN_ONE(y) GN_ONE(z) GN_ONE(w)                        \
+            erd::st4(dc + (OFF), o);                                       \
+        }
+    int64_t r = r0 + rl;
+#pragma unroll 1
+    for (; r + 4 * (GN_FLIGHT - 1) < r1; r += 4 * GN_FLIGHT) {      // GN_FLIGHT rows of both tensors in flight per thread
+        const int64_t off = ((int64_t)n * A + r) * C + c4 * 4;
+        decltype(ld4_raw(c)) vv[GN_FLIGHT], dd[GN_FLIGHT];
+#pragma unroll
+        for (int q = 0; q < GN_FLIGHT; ++q) {
+            vv[q] = ld4_raw(c + off + (int64_t)q * 4 * C);
+            dd[q] = ld4_raw(dy + off + (int64_t)q * 4 * C);
+        }
+        loads_first(vv, dd);
+#pragma unroll
+        for (int q = 0; q < GN_FLIGHT; ++q) GN_ROW(cooked(vv[q]), cooked(dd[q]), off + (int64_t)q * 4 * C)
     }
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    for (; r < r1; r += 4) {
+        const int64_t off = ((int64_t)n * A + r) * C + c4 * 4;
+        GN_ROW(erd::ld4(c + off), erd::ld4(dy + off), off)
+    }
+#undef GN_ROW
+#undef GN_ONE
 }
 
 GnChunks make_chunks(const erd_levels* lv, int rows = GN_ROWS) {
@@ -616,6 +702,57 @@ __global__ __launch_bounds__(256) void upsample_add_bwd_kernel(const T* __restri
     }
 }
 
+// out[c] += sum over rows of x[r][c] for C % 4 == 0, in the shape of relu_bwd_colsum_kernel: block (x = row range, y = group of cw4
+// float4 columns), thread (column tid % cw4, row lane tid / cw4) with four rows in flight, one combine through LDS, one atomic per
+// channel and workgroup.  cw4 need not divide 256 (17 columns at the 68-channel head: 15 row lanes, one thread idle).  Adds to one
+// address retire at ~40 per microsecond, so the grid is COLSUM_WGS long row ranges: the one-thread-per-channel form below, with a
+// workgroup per 64 rows, spent its 36 us on 1 400 adds per channel.
+#ifndef COLSUM_WGS
+#define COLSUM_WGS 128
+#endif
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_vec_kernel(const T* __restrict__ x, int64_t rows, int C4, float* __restrict__ out,
+                                                         int64_t rows_per_block, int cw4) {
+    __shared__ float4 red[256];
+    const int lanes = 256 / cw4;
+    const int cl = threadIdx.x % cw4, rl = threadIdx.x / cw4;
+    const int c4 = blockIdx.y * cw4 + cl;
+    const int64_t r_begin = blockIdx.x * rows_per_block, r_end = min(rows, r_begin + rows_per_block);
+    const int64_t C = (int64_t)C4 * 4;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (rl < lanes && c4 < C4) {
+        const T* xc = x + c4 * 4;
+        int64_t r = r_begin + rl;
+        for (; r + 3 * lanes < r_end; r += 4 * lanes) {
+            float4 v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = erd::ld4(xc + (r + q * lanes) * C);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { s.x += v[q].x; s.y += v[q].y; s.z += v[q].z; s.w += v[q].w; }
+        }
+        for (; r < r_end; r += lanes) {
+            const float4 v = erd::ld4(xc + r * C);
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    __shared__ __attribute__((aligned(16))) float sums[256];
+    if (rl == 0) {
+        float4 t = red[cl];
+        for (int j = 1; j < lanes; ++j) {
+            const float4 v = red[cl + j * cw4];
+            t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
+        }
+        *reinterpret_cast<float4*>(&sums[cl * 4]) = t;
+    }
+    __syncthreads();
+    // one lane per channel: the adds of a workgroup are contiguous bytes (they all queue on the same C addresses)
+    const int ch = blockIdx.y * cw4 * 4 + threadIdx.x;
+    if (threadIdx.x < cw4 * 4 && ch < C) atomicAdd(out + ch, sums[threadIdx.x]);
+}
+
+// any C, 4-byte loads: the path of a channel count that is no multiple of 4 (a 70-class head) or of rows that are not 16-byte aligned
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, int64_t rows, int C,
                                                      float* __restrict__ out, int rows_per_block) {
@@ -651,6 +788,10 @@ __global__ __launch_bounds__(256) void level_scale_kernel(const float* __restric
     for (int64_t i = threadIdx.x; i < cnt; i += 256) y[base + i] = x[base + i] * a;
 }
 
+// VEC (C % 4 == 0 and 16-byte aligned buffers: a chunk then starts and ends on a float4): 16-byte accesses, four in flight per thread.
+// (The forward above keeps its 4-byte form: with float4s it measured 13.3 us against 13.0 on the head's 49 MB, a launch of that size
+// being mostly ramp and tail.)
+template <bool VEC>
 __global__ __launch_bounds__(256) void level_scale_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                               const float* __restrict__ alphas, float* __restrict__ dx,
                                                               float* __restrict__ dalphas, int64_t A, int C,
@@ -661,10 +802,34 @@ __global__ __launch_bounds__(256) void level_scale_bwd_kernel(const float* __res
     const float a = alphas[s];
     const int64_t base = ((int64_t)n * A + r0) * C, cnt = (r1 - r0) * C;
     float acc = 0.f;
-    for (int64_t i = threadIdx.x; i < cnt; i += 256) {
-        const float g = dy[base + i];
-        acc += g * x[base + i];
-        dx[base + i] = g * a;
+    if constexpr (VEC) {
+        const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x + base);
+        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(dy + base);
+        float4* __restrict__ dx4 = reinterpret_cast<float4*>(dx + base);
+        const int64_t cnt4 = cnt >> 2;
+#define LS_ONE(G, X, I)                                                                        \
+        {                                                                                      \
+            const float4 g = G, v = X;                                                         \
+            acc += g.x * v.x; acc += g.y * v.y; acc += g.z * v.z; acc += g.w * v.w;            \
+            dx4[I] = make_float4(g.x * a, g.y * a, g.z * a, g.w * a);                          \
+        }
+        int64_t i = threadIdx.x;
+        for (; i + 3 * 256 < cnt4; i += 4 * 256) {
+            raw_f32x4 gg[4], vv[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { gg[q] = ld4_raw(dy + base + 4 * (i + q * 256)); vv[q] = ld4_raw(x + base + 4 * (i + q * 256)); }
+            loads_first(gg, vv);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) LS_ONE(cooked(gg[q]), cooked(vv[q]), i + q * 256)
+        }
+        for (; i < cnt4; i += 256) LS_ONE(g4[i], x4[i], i)
+#undef LS_ONE
+    } else {
+        for (int64_t i = threadIdx.x; i < cnt; i += 256) {
+            const float g = dy[base + i];
+            acc += g * x[base + i];
+            dx[base + i] = g * a;
+        }
     }
     acc = erd::wave_sum(acc);
     __shared__ float red[4];
@@ -1280,6 +1445,15 @@ extern "C" int erd_colsum(const void* x, int64_t rows, int C, float* out, int ac
     hipStream_t st = (hipStream_t)stream;
     if (!accumulate) ERD_ZERO_ASYNC(out, sizeof(float) * C, st);
     if (rows == 0) return 0;
+    if (C % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & (map_type == ERD_BF16 ? 7 : 15)) == 0) {
+        const int C4 = C / 4, cw4 = C4 < 64 ? C4 : 64, gy = (C4 + cw4 - 1) / cw4, lanes = 256 / cw4;
+        const int ranges = COLSUM_WGS / gy > 0 ? COLSUM_WGS / gy : 1;
+        const int64_t unit = 4 * lanes;                                 // rows one pass of the unrolled loop covers
+        const int64_t rpb = ((rows + ranges - 1) / ranges + unit - 1) / unit * unit;
+        ERD_MAP(map_type, hipLaunchKernelGGL(colsum_vec_kernel<T>, dim3((unsigned)((rows + rpb - 1) / rpb), gy), dim3(256), 0, st,
+                                             (const T*)x, rows, C4, out, rpb, cw4));
+        return erd::check_launch("colsum");
+    }
     int rpb = 64;
     while ((rows + rpb - 1) / rpb > 2048) rpb *= 2;
     ERD_MAP(map_type, hipLaunchKernelGGL(colsum_kernel<T>, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, st,
@@ -1310,8 +1484,12 @@ extern "C" int erd_level_scale_bwd(const float* x, const float* dy, const float*
     hipStream_t st = (hipStream_t)stream;
     const GnChunks ch = make_chunks(lv);
     ERD_ZERO_ASYNC(dalphas, sizeof(float) * lv->nseg, st);
-    hipLaunchKernelGGL(level_scale_bwd_kernel, dim3(ch.start[lv->nseg], N), dim3(256), 0, st, x, dy, alphas, dx,
-                       dalphas, A, C, *lv, ch);
+    if (C % 4 == 0 && aligned16(x, dy) && aligned16(dx, dx))
+        hipLaunchKernelGGL(level_scale_bwd_kernel<true>, dim3(ch.start[lv->nseg], N), dim3(256), 0, st, x, dy, alphas, dx,
+                           dalphas, A, C, *lv, ch);
+    else
+        hipLaunchKernelGGL(level_scale_bwd_kernel<false>, dim3(ch.start[lv->nseg], N), dim3(256), 0, st, x, dy, alphas, dx,
+                           dalphas, A, C, *lv, ch);
     return erd::check_launch("level_scale_bwd");
 }
 

@@ -13,6 +13,7 @@
 //     conv_thin.hip   ERD_THIN_NOSTORE ERD_THIN_NOMFMA                                                    thin-K kernel: no output stores / no MFMAs
 //     wgrad_wino.hip  ERD_WW_NOMFMA  ERD_WW_NOLOAD  ERD_WW_NOSPLIT  ERD_WW_NOTABLE                     Winograd-domain weight gradient: K loop without a phase
 //     elementwise.hip ERD_GN_NOSTATS                                                                    GroupNorm without its statistics pass
+//                     ERD_GN_BWD_NOATOMICS                                                              gn_bwd_stats_kernel without its final atomics
 //   accuracy probe (results differ in the last bits)
 //     conv_mfma.hip, conv_thin.hip   ERD_X3_NINE      all nine limb products instead of six
 //   tracing (results unchanged; s_memtime stamps + a device-side trace buffer)
@@ -20,13 +21,14 @@
 //     conv_thin.hip   ERD_THIN_TRACE   (erd_thin_trace)
 //   tuning parameters (results unchanged; defaults are the shipped values)
 //     ERD_SGB  ERD_W3X3_MINW  ERD_WINO_NCH  ERD_WINO_DATA_PRIO  ERD_WINO_MMA_PRIO  ERD_WX3_RD
+//     elementwise.hip COLSUM_WGS (row ranges of colsum_vec_kernel)
 #pragma once
 
 #if defined(ERD_X3_NOMFMA) || defined(ERD_X3_NOLOAD) || defined(ERD_X3_NOBREAD) || defined(ERD_X3_NOVALU) || defined(ERD_X3_NOSYNC) || \
     defined(ERD_IG_NOMFMA) || defined(ERD_IG_NOLOAD) || defined(ERD_IG_NOFRAG) || defined(ERD_IG_NOSYNC) || defined(ERD_WX3_NOMFMA) ||    \
     defined(ERD_WX3_NOSPLIT) || defined(ERD_WX3_NOLOAD) || defined(ERD_WX3_VREAD1) || defined(ERD_WX3_VWRITE1) || defined(ERD_THIN_NOSTORE) || defined(ERD_THIN_NOMFMA) || defined(ERD_WX3_NORAW) || defined(ERD_WINO_GNPROBE) || defined(ERD_GN_NOSTATS) || defined(ERD_X3_NINE) || \
     defined(ERD_IGEMM_TRACE) || defined(ERD_WINO_TRACE) || defined(ERD_THIN_TRACE) || defined(ERD_WW_NOMFMA) || defined(ERD_WW_NOLOAD) || \
-    defined(ERD_WW_NOSPLIT) || defined(ERD_WW_NOTABLE)
+    defined(ERD_WW_NOSPLIT) || defined(ERD_WW_NOTABLE) || defined(ERD_GN_BWD_NOATOMICS)
 #define ERD_PROBE_BUILD 1
 extern "C" __attribute__((weak, visibility("default"))) int erd_probe_build_marker = 1;
 #endif
