@@ -85,15 +85,15 @@ def maps(case):
     return SIZES, SIZES
 
 
-@functools.lru_cache(maxsize=None)
-def inputs(name):
-    """everything a launch of the case reads, fp32 on the CPU, from a seeded generator: x [N, h, w, K] per segment in {-1, 0, 1}, the
-    FORWARD weight w in {-2 .. 2} (fwd: [C, k, k, K]; dgrad: [K, k, k, C], the input gradient contracts over its output channels),
-    and the epilogue's operands"""
-    case = BY_NAME[name]
-    g = torch.Generator().manual_seed(sum(map(ord, name)))
+ALPHAS = (0.5, 2.0)
+
+
+def build_inputs(case, ins, outs, alphas=ALPHAS):
+    """everything a launch of the case reads, fp32 on the CPU, from a generator seeded by the case's name: x [N, h, w, K] per segment
+    in {-1, 0, 1}, the FORWARD weight w in {-2 .. 2} (fwd: [C, k, k, K]; dgrad: [K, k, k, C], the input gradient contracts over its
+    output channels), and the epilogue's operands.  `ins` / `outs`: map sizes per segment (tests/thin_refs.py passes its own)"""
+    g = torch.Generator().manual_seed(sum(map(ord, case.name)))
     ri = lambda lo, hi, *shape: torch.randint(lo, hi + 1, shape, generator=g).float()
-    ins, outs = maps(case)
     d = dict(x=[ri(-1, 1, N, h, w, case.K) for h, w in ins])
     d["w"] = ri(-2, 2, *((case.C, case.k, case.k, case.K) if case.form == "fwd" else (case.K, case.k, case.k, case.C)))
     oshape = [(N, h, w, case.C) for h, w in outs]
@@ -104,7 +104,7 @@ def inputs(name):
     if "R" in e or "P" in e:
         d["res"] = [ri(-4, 4, *s) if ("R" in e or i == 0) else None for i, s in enumerate(oshape)]
     if "a" in e:
-        d["alpha"] = [torch.tensor([v]) for v in (0.5, 2.0)][:len(oshape)]
+        d["alpha"] = [torch.tensor([v]) for v in alphas][:len(oshape)]
     if "A" in e:
         d["base"] = [ri(-4, 4, *s) for s in oshape]
     if "m" in e:
@@ -112,17 +112,21 @@ def inputs(name):
     return d
 
 
+@functools.lru_cache(maxsize=None)
+def inputs(name):
+    """build_inputs of a case of this table, on its maps"""
+    case = BY_NAME[name]
+    return build_inputs(case, *maps(case))
+
+
 def acc_bound(case):
     """no partial sum of the GEMM can exceed this magnitude"""
     return 2 * case.k * case.k * case.K
 
 
-@functools.lru_cache(maxsize=None)
-def expected(name):
-    """(outputs per segment in the storage type of the case, column sums [C] or None): the one right answer"""
-    case = BY_NAME[name]
-    d = inputs(name)
-    ins, outs = maps(case)
+def build_expected(case, d, outs):
+    """(outputs per segment in the storage type of the case, column sums [C] or None): the one right answer for the inputs d.  The
+    column sums add the exact values, BEFORE a bf16-stored output is rounded: both kernels sum their fp32 results."""
     res = []
     for i, x in enumerate(d["x"]):
         xn, p = x.permute(0, 3, 1, 2).double(), case.k // 2
@@ -149,6 +153,13 @@ def expected(name):
         res.append(y)
     cs = sum(y.sum((0, 1, 2)) for y in res).float() if ("c" in case.epi or "C" in case.epi) else None
     return [y.float().bfloat16() if case.ob else y.float() for y in res], cs
+
+
+@functools.lru_cache(maxsize=None)
+def expected(name):
+    """build_expected of a case of this table"""
+    case = BY_NAME[name]
+    return build_expected(case, inputs(name), maps(case)[1])
 
 
 # ---------------------------------------------------------------------------------------------
