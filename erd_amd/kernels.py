@@ -833,6 +833,12 @@ class ParamPrep:
 
     def register(self, key, kind: int, src: Tensor, rowscale: Optional[Tensor], out: Tensor, Cout: int, ntaps: int, Cin: int,
                  flip: int, owner, level: int) -> None:
+        if kind not in (0, 1, 2, 3, 4) or min(Cout, ntaps, Cin) <= 0:
+            raise _lib.ErdHipError(f"weight_prep: bad item (kind={kind}, Cout={Cout}, ntaps={ntaps}, Cin={Cin})")
+        if kind in (2, 4) and (Cin % 16 != 0 or ntaps != 9):
+            # erd_wino_weights(_x3) refuses these on the host; the batched kernel reads its items from device memory and cannot:
+            # with a ragged Cin its image index runs past the destination
+            raise _lib.ErdHipError(f"weight_prep: a Winograd image needs 9 taps and Cin a multiple of 16 (ntaps={ntaps}, Cin={Cin})")
         r = _PrepRecipe()
         r.kind, r.src, r.rowscale, r.out, r.Cout, r.ntaps, r.Cin, r.flip = kind, src, rowscale, out, Cout, ntaps, Cin, flip
         r.owner, r.version, r.level, r.stamp = owner, owner._version, level, -1
