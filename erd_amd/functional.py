@@ -7,7 +7,7 @@ views are maps.  Weights are ``nn.Parameter``s of logical shape OIHW in channels
 ``[Cout][kh][kw][Cin]`` as the kernels want them (checkpoint ABI = the reference's OIHW keys/shapes)."""
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch.autograd import Function
@@ -204,6 +204,53 @@ def _emit_wgrad_wino(w: Tensor, part: Tensor, S: int, wk: Tensor):
     return _to_oihw(dWk)
 
 
+def _emit_bn_grads(rowdot: Optional[Tensor], dbeta: Tensor, mean: Tensor, var: Tensor, eps: float, need_g: bool, need_b: bool,
+                   g: Optional[Tensor] = None, b: Optional[Tensor] = None, dgamma_out: Optional[Tensor] = None):
+    """d gamma and d beta of a convolution's folded BN, from the `rowdot` of its weight-gradient reduce (_emit_wgrad) and the column
+    sums `dbeta` of its output gradient: a [C] vector (which may BE d beta's flat slot) or the replicated [copies, C] accumulator of a
+    gradient convolution's epilogue, which is folded here -- by the d gamma launch where there is one.  Destinations: `g` / `b` name
+    the parameters whose flat slots (zero at this point: a plain store is the accumulation) take the results and who then report
+    (_sunk); a result without a slot goes back to the caller (d gamma in `dgamma_out` when given).  Returns (d gamma, d beta), None
+    where the slot took it or it is not needed.  Allocates on the current stream: call it INSIDE the _Trail / _Fork of its launches."""
+    gs, bs = _sink(g) if need_g else None, _sink(b) if need_b else None
+    dgamma, rep = None, dbeta.dim() == 2
+    if need_g:
+        fold = None if not rep else (bs if bs is not None else torch.empty_like(dbeta[0]))
+        dgamma = K.bn_dgamma(rowdot, dbeta, mean, var, eps, out=gs if gs is not None else dgamma_out, dbeta_out=fold)
+        if gs is not None:
+            _sunk(g)
+            dgamma = None
+        if rep:
+            dbeta = fold
+    elif rep:
+        dbeta = dbeta.sum(0)
+    if not need_b or bs is None:
+        return dgamma, (dbeta if need_b else None)
+    if dbeta.data_ptr() != bs.data_ptr():   # (the projection shortcut shares conv3's column sums; a fold lands in the slot itself)
+        bs.add_(dbeta)
+    _sunk(b)
+    return dgamma, None
+
+
+class _Wgrad(NamedTuple):
+    """one collected weight gradient of _WgradGroups: the arguments of _bottleneck_backward's wgrad() and `single`, which launches it alone"""
+    single: Callable[[], None]
+    xin: Tensor
+    dz: Tensor
+    k: int
+    s: int
+    pad: int
+    scale: Tensor
+    dbeta: Tensor
+    w: Tensor
+    g: Tensor
+    b: Tensor
+    mean: Tensor
+    var: Tensor
+    need_g: bool
+    need_b: bool
+
+
 class _WgradGroups:
     """The weight gradients of one stage's backward pass, collected by shape.  add() takes a weight gradient of _bottleneck_backward's
     wgrad() whose needed gradients all have a flat slot (the ones that trail under WGRAD_TRAIL); a key -- (k, stride, pad, geometry of x and dz) -- is
@@ -227,10 +274,10 @@ class _WgradGroups:
         return WGRAD_GROUPED and CAPTURE_ORIGIN is None and K.COMPUTE == "f32x3" and K.WGRAD_X3 and K.WGRAD_X3_GENERIC and xin.dtype == torch.float32 \
             and dz.dtype == torch.float32 and _os.environ.get("ERD_WGRAD_ROW3", "1") != "0"
 
-    def add(self, single, xin, dz, k, s, pad, scale, dbeta, prm, need3) -> None:
-        key = (k, s, pad, xin.shape, xin.stride(), dz.shape, dz.stride())
+    def add(self, m: _Wgrad) -> None:
+        key = (m.k, m.s, m.pad, m.xin.shape, m.xin.stride(), m.dz.shape, m.dz.stride())
         q = self.keys.setdefault(key, [])
-        q.append((single, xin, dz, k, s, pad, scale, dbeta, prm, need3))
+        q.append(m)
         if len(q) == WGRAD_GROUP_CAP:
             self._launch(self.keys.pop(key))
 
@@ -241,32 +288,16 @@ class _WgradGroups:
     def _launch(self, q) -> None:
         self.launches.append(len(q))
         if len(q) == 1:
-            q[0][0]()
+            q[0].single()
             return
-        _, _, _, k, s, pad = q[0][:6]
-        with (_Trail(self.dev, *[t for m in q for t in (m[1], m[2], m[6], m[7])]) if WGRAD_TRAIL else _contextlib.nullcontext()):
-            part, S = K.conv_wgrad_partials_grouped([[m[1]] for m in q], [[m[2]] for m in q], k, s, pad)
-            wks = [ohwi(m[8][0]) for m in q]
-            rowdots = [K.zeros_f32(m[6].numel(), m[6].device) if m[9][1] else None for m in q]
-            K.wgrad_reduce_grouped(part, S, wks, [m[6] for m in q], [ohwi(_sink(m[8][0])) for m in q], True, rowdots, rowdot_zeroed=True)
-            for m, rowdot in zip(q, rowdots):
-                (w, g, b, mean, var), (_, need_g, need_b), dbeta = m[8], m[9], m[7]
-                _sunk(w)
-                if need_g:
-                    rep = dbeta.dim() == 2
-                    bs_fold = (_sink(b) if need_b else None) if rep else None
-                    fold = None if not rep else (bs_fold if bs_fold is not None else torch.empty_like(dbeta[0]))
-                    K.bn_dgamma(rowdot, dbeta, mean, var, self.eps, out=_sink(g), dbeta_out=fold)
-                    _sunk(g)
-                    if rep:
-                        dbeta = fold
-                elif dbeta.dim() == 2:
-                    dbeta = dbeta.sum(0)
-                if need_b:
-                    bs = _sink(b)
-                    if dbeta.data_ptr() != bs.data_ptr():   # (the projection shortcut shares conv3's column sums)
-                        bs.add_(dbeta)
-                    _sunk(b)
+        with (_Trail(self.dev, *[t for m in q for t in (m.xin, m.dz, m.scale, m.dbeta)]) if WGRAD_TRAIL else _contextlib.nullcontext()):
+            part, S = K.conv_wgrad_partials_grouped([[m.xin] for m in q], [[m.dz] for m in q], q[0].k, q[0].s, q[0].pad)
+            rowdots = [K.zeros_f32(m.scale.numel(), m.scale.device) if m.need_g else None for m in q]
+            K.wgrad_reduce_grouped(part, S, [ohwi(m.w) for m in q], [m.scale for m in q], [ohwi(_sink(m.w)) for m in q], True, rowdots,
+                                   rowdot_zeroed=True)
+            for m, rowdot in zip(q, rowdots):      # (every needed gradient of a member has a flat slot: nothing comes back)
+                _sunk(m.w)
+                _emit_bn_grads(rowdot, m.dbeta, m.mean, m.var, self.eps, m.need_g, m.need_b, m.g, m.b)
 
 
 def _bn_fold_cached(gamma, beta, mean, var, eps):
@@ -394,6 +425,19 @@ def _wgrad_plain(w: Tensor, xs, dzs, k: int, stride: int, pad: int, keep=(), tra
     return run()
 
 
+def _conv_bn_act(x: Tensor, prm, k: int, stride: int, pad: int, res: Optional[Tensor], relu: bool, eps: float):
+    """[relu]( conv(x, w) * scale + shift [+ res] ) into a new map, prm = (w, gamma, beta, mean, var) of the convolution and its
+    frozen-statistics BN: (out, scale)"""
+    w, gamma, beta, mean, var = prm
+    wk = ohwi(w)
+    scale, shift = _bn_fold_cached(gamma, beta, mean, var, eps)
+    N, H, W_, _ = x.shape
+    OH, OW = K.conv_out_size(H, k, stride, pad), K.conv_out_size(W_, k, stride, pad)
+    out = torch.empty((N, OH, OW, wk.shape[0]), dtype=x.dtype, device=x.device)      # maps keep their storage type
+    K.conv_forward([x], wk, [out], k, stride, pad, scale=scale, shift=shift, res=None if res is None else [res], relu=relu)
+    return out, scale
+
+
 class ConvBNAct(Function):
     """y = [relu]( conv(x, w) * scale + shift [+ res] ) with scale/shift folded from a frozen-statistics BN
     (resnet.py:263-302 Bottleneck; norm_eval=True resnet.py:648-657).  gamma/beta still receive gradients
@@ -402,13 +446,7 @@ class ConvBNAct(Function):
     @staticmethod
     def forward(ctx, x, w, gamma, beta, mean, var, res, k: int, stride: int, pad: int, relu: bool, eps: float):
         K.RECORDED = any(ctx.needs_input_grad)      # see kernels.WINO_TRAIN_FWD
-        wk = ohwi(w)
-        scale, shift = _bn_fold_cached(gamma, beta, mean, var, eps)
-        N, H, W_, _ = x.shape
-        OH, OW = K.conv_out_size(H, k, stride, pad), K.conv_out_size(W_, k, stride, pad)
-        out = torch.empty((N, OH, OW, wk.shape[0]), dtype=x.dtype, device=x.device)      # maps keep their storage type
-        K.conv_forward([x], wk, [out], k, stride, pad, scale=scale, shift=shift,
-                       res=None if res is None else [res], relu=relu)
+        out, scale = _conv_bn_act(x, (w, gamma, beta, mean, var), k, stride, pad, res, relu, eps)
         ctx.cfg = (k, stride, pad, relu, eps, res is not None)
         ctx.save_for_backward(x, w, mean, var, scale, out)
         return out
@@ -430,8 +468,7 @@ class ConvBNAct(Function):
             with fork:
                 part, S = K.conv_wgrad_partials([x], [dz], k, stride, pad, cardinality=card)
                 dW = _emit_wgrad(w, part, S, wk, scale, rowdot)
-                if need_g:
-                    K.bn_dgamma(rowdot, dbeta, mean, var, eps, out=dgamma)
+                _emit_bn_grads(rowdot, dbeta, mean, var, eps, need_g, False, dgamma_out=dgamma)      # d beta IS the column sums
         dx = None
         if need_x and card > 1:      # the grouped kernel reads the parameter and the row scale directly
             dx = torch.empty_like(x)
@@ -450,7 +487,7 @@ class DeformConvBNAct(Function):
     """conv2 of a DCN bottleneck (mmcv DeformConv2dPack as resnet.py:174-197 builds it, + the block's frozen-statistics BN and ReLU):
         offset = conv_offset(x) (3x3, C -> 18, bias, the layer's stride);  y = [relu](bn(col(x, offset) . W^T))
     The offset convolution runs on the launch form of the head outputs (3x3 + bias, Cout not a multiple of 16: its gradients run at
-    Cp = 32 on zero-padded copies, functional.HeadConvBias); the sampling and its backward are csrc/conv_deform.hip; the contraction is
+    Cp = 32 on zero-padded copies, _padded_cout_backward); the sampling and its backward are csrc/conv_deform.hip; the contraction is
     a 1x1 convolution over the 9 * C columns.  Backward gathers the columns again (they are not kept: DESIGN 2) and chains the two
     gradients of x in ONE buffer: zero, the atomic scatter of the sampling, then the offset convolution's input gradient on top."""
 
@@ -484,96 +521,78 @@ class DeformConvBNAct(Function):
             rowdot = K.zeros_f32(scale.numel(), scale.device) if need_g else None
             part, S = K.deform_conv3x3_wgrad_partials(x, offset, dz, stride)
             dW = _emit_wgrad(w, part, S, wk, scale, rowdot)
-            if need_g:
-                dgamma = K.bn_dgamma(rowdot, dbeta, mean, var, eps)
+            dgamma, _ = _emit_bn_grads(rowdot, dbeta, mean, var, eps, need_g, False)      # d beta IS the column sums
         if need_x or need_wo or need_bo:
             dx = torch.zeros_like(x)
             doffset = K.deform_conv3x3_dgrad(dz, wk, scale, x, offset, stride, dx)
-            # the offset convolution's gradients contract over its 18 output channels: at Cp = 32 on zero-padded copies
-            wok = ohwi(w_off)
-            Cp = 32
-            dop = K.pad_channels(doffset, Cp)
-            if need_wo:
-                part, S = K.conv_wgrad_partials([x], [dop], 3, stride, 1)
-                sink = _sink(w_off)
-                if sink is not None:
-                    K.wgrad_reduce_rows(part, S, Cp, ohwi(sink), True)
-                    _sunk(w_off)
-                else:
-                    dWk = torch.empty_like(wok)
-                    K.wgrad_reduce_rows(part, S, Cp, dWk, False)
-                    dWo = _to_oihw(dWk)
-            if need_bo:
-                dbo = _bias_grad(ctx.bias_param, doffset)
-            if need_x:
-                wp = K.pad_channels(wok.reshape(1, -1), Cp * wok[0].numel()).view(Cp, *wok.shape[1:])
-                K.conv_dgrad([dop], K.weight_transpose(wp), [dx], 3, stride, 1, accumulate=True)
-            else:
+            # the offset convolution's gradients contract over its 18 output channels (Cp = 32); its input gradient lands on top of dx
+            dWo, dbo = _padded_cout_backward(w_off, ctx.bias_param, doffset, lambda t: [t], [x], [dx] if need_x else None, stride,
+                                             need_wo, need_bo, accumulate=True)
+            if not need_x:
                 dx = None
         return dx, dW, dWo, dbo, dgamma, (dbeta if need_b else None), None, None, None, None, None
 
 
-class BottleneckFn(Function):
-    """A whole ResNet bottleneck (resnet.py:263-302) as ONE autograd node with a hand-scheduled backward:
-        o1 = relu(bn1(conv1 x)); o2 = relu(bn2(conv2 o1)); y = relu(bn3(conv3 o2) + shortcut(x))
-    Backward: only y's ReLU needs its own pass (its gradient has several producers); the masks of o2 / o1 and the
-    d-beta column sums are applied in the EPILOGUE of the input-gradient GEMM that produces their gradient, and the
-    identity shortcut's gradient is the residual operand of conv1's input-gradient GEMM -- no stand-alone ReLU
-    backward, no gradient-accumulation kernels inside the block."""
+def _padded_cout_backward(w: Tensor, b: Tensor, dy: Tensor, maps, xs, dxs, stride: int, need_w: bool, need_b: bool,
+                          accumulate: bool = False):
+    """Backward of a 3x3 / pad-1 convolution + bias whose Cout is not a multiple of 4 (a 70- or 50-class gfl_cls, the 18 offset
+    channels of a DCN): both GEMM gradients contract over Cout, which the kernels take in 4-channel groups.  They run at
+    Cp = round_up(Cout, 16) -- the 80-class head's launches for 70 classes -- on zero-padded copies of dy and of the weight; the padding
+    channels contribute exact zeros.  The weight gradient reduces only rows [0, Cout) of the [S, Cp, 9 * Cin] partial slabs; the bias
+    gradient is the column sum over Cout.  `maps(t)`: the maps of a buffer laid out like dy; xs: the input maps; dxs: the maps the input
+    gradient is written (`accumulate`: added) to, None: not needed.  Order: weight, bias, input.  Returns (dW, db)."""
+    wk = ohwi(w)
+    Cp = (wk.shape[0] + 15) // 16 * 16
+    dzs = maps(K.pad_channels(dy, Cp))
+    dW = db = None
+    if need_w:
+        part, S = K.conv_wgrad_partials(xs, dzs, 3, stride, 1)
+        sink = _sink(w)
+        if sink is not None:
+            K.wgrad_reduce_rows(part, S, Cp, ohwi(sink), True)
+            _sunk(w)
+        else:
+            dWk = torch.empty_like(wk)
+            K.wgrad_reduce_rows(part, S, Cp, dWk, False)
+            dW = _to_oihw(dWk)
+    if need_b:
+        db = _bias_grad(b, dy)
+    if dxs is not None:
+        wp = K.pad_channels(wk.reshape(1, -1), Cp * wk[0].numel()).view(Cp, *wk.shape[1:])
+        K.conv_dgrad(dzs, K.weight_transpose(wp), dxs, 3, stride, 1, accumulate=accumulate)
+    return dW, db
 
-    @staticmethod
-    def forward(ctx, x, stride: int, eps: float, *params):
-        K.RECORDED = any(ctx.needs_input_grad)      # see kernels.WINO_TRAIN_FWD
-        # params: (w,g,b,mean,var) x {conv1,conv2,conv3[,downsample]}
-        has_down = len(params) == 20
-        P = [params[5 * i:5 * i + 5] for i in range(4 if has_down else 3)]
-        dev = x.device
 
-        def cba(inp, prm, k, s, pad, res, relu):
-            w, g, b, m, v = prm
-            wk = ohwi(w)
-            scale, shift = _bn_fold_cached(g, b, m, v, eps)
-            N, H, W_, _ = inp.shape
-            out = torch.empty((N, K.conv_out_size(H, k, s, pad), K.conv_out_size(W_, k, s, pad), wk.shape[0]),
-                              dtype=inp.dtype, device=dev)
-            K.conv_forward([inp], wk, [out], k, s, pad, scale=scale, shift=shift,
-                           res=None if res is None else [res], relu=relu)
-            return out, scale
+def _per_conv(bp):
+    """a block's flat parameter list -> (w, gamma, beta, mean, var) per convolution: conv1, conv2, conv3[, downsample]"""
+    return [bp[i:i + 5] for i in range(0, len(bp), 5)]
 
-        o1, s1 = cba(x, P[0], 1, 1, 0, None, True)
-        o2, s2 = cba(o1, P[1], 3, stride, 1, None, True)
-        sd = None
-        idn = x
-        if has_down:
-            idn, sd = cba(x, P[3], 1, stride, 0, None, False)
-        y, s3 = cba(o2, P[2], 1, 1, 0, idn, True)
-        ctx.cfg = (stride, eps, has_down)
-        ctx.save_for_backward(x, o1, o2, y, s1, s2, s3, *( [sd] if has_down else []), *params)
-        return y
 
-    @staticmethod
-    def backward(ctx, dy):
-        stride, eps, has_down = ctx.cfg
-        saved = ctx.saved_tensors
-        x, o1, o2, y, s1, s2, s3 = saved[:7]
-        off = 7
-        sd = None
-        if has_down:
-            sd = saved[7]
-            off = 8
-        params = saved[off:]
-        P = [params[5 * i:5 * i + 5] for i in range(4 if has_down else 3)]
-        need = ctx.needs_input_grad
-        b3 = P[2][2]
-        s_ = _sink(b3) if need[3 + 5 * 2 + 2] else None
-        dz3, db3 = K.relu_bwd_colsum(y, dy.contiguous(), True, colsum_into=s_ if s_ is not None else K.zeros_f32(y.shape[3], x.device))
-        dx, grads = _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, list(need[3:]), need[0], stride, eps, dz3, db3)
-        return (dx, None, None, *grads)
+def _bottleneck_forward(h: Tensor, bp, stride: int, eps: float) -> list:
+    """A ResNet bottleneck (resnet.py:263-302):
+        o1 = relu(bn1(conv1 h)); o2 = relu(bn2(conv2 o1)); y = relu(bn3(conv3 o2) + shortcut(h))
+    Returns what its backward reads, [h, o1, o2, y, s1, s2, s3(, sd)]: the maps and the folded BN scales (sd: the projection's)."""
+    P = _per_conv(bp)
+    o1, s1 = _conv_bn_act(h, P[0], 1, 1, 0, None, True, eps)
+    o2, s2 = _conv_bn_act(o1, P[1], 3, stride, 1, None, True, eps)
+    idn, sd = _conv_bn_act(h, P[3], 1, stride, 0, None, False, eps) if len(P) == 4 else (h, None)
+    y, s3 = _conv_bn_act(o2, P[2], 1, 1, 0, idn, True, eps)
+    return [h, o1, o2, y, s1, s2, s3] + ([] if sd is None else [sd])
+
+
+def _exit_relu_backward(y: Tensor, dy: Tensor, b3: Tensor, need_b3: bool):
+    """The stand-alone ReLU backward of a block whose output gradient arrives from outside the chain: (dz3, its column sums -- in
+    beta3's flat slot where it has one, else in fresh zeros)"""
+    s_ = _sink(b3) if need_b3 else None
+    return K.relu_bwd_colsum(y, dy, True, colsum_into=s_ if s_ is not None else K.zeros_f32(y.shape[3], y.device))
 
 
 def _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_p, need_x, stride, eps, dz3, db3, out_mask=None, groups=None):
-    """Backward of one bottleneck given dz3 = dy * (y > 0) and its column sums db3 (a [C] vector that may BE d beta's flat slot,
-    or a replicated [copies, C] accumulator of a gradient convolution's epilogue).  need_p: needs-gradient flags of the block's
+    """Hand-scheduled backward of one bottleneck.  Only y's ReLU needs its own pass (its gradient has several producers); the masks
+    of o2 / o1 and the d-beta column sums are applied in the EPILOGUE of the input-gradient GEMM that produces their gradient, and the
+    identity shortcut's gradient is the residual operand of conv1's input-gradient GEMM -- no stand-alone ReLU backward, no
+    gradient-accumulation kernels inside the block.  Given: dz3 = dy * (y > 0) and its column sums db3 (a [C] vector that may BE d beta's
+    flat slot, or a replicated [copies, C] accumulator of a gradient convolution's epilogue).  need_p: needs-gradient flags of the block's
     parameters, 5 per convolution (w, gamma, beta, mean, var).  Returns (dx, grads).  With `out_mask` (the block's own input x,
     which is the previous block's post-ReLU output) the last input-gradient launch ALSO applies that ReLU's mask and column-sums
     the result into a fresh replicated accumulator: it then returns ((dz3 of the previous block, its db3), grads) -- the
@@ -589,52 +608,21 @@ def _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_p, need_x, stride, e
         """dW (scaled by the folded BN), d gamma, d beta of conv `idx`"""
         w, g, b, m, v = P[idx]
         base = 5 * idx
-        if not (need_p[base] or need_p[base + 1] or need_p[base + 2]):
+        need = tuple(need_p[base:base + 3])
+        if not any(need):
             return
         wk = ohwi(w)
-        trail = None
-        sunk = all((not need_p[base + q]) or _sink(t) is not None for q, t in enumerate((w, g, b)))
-        if collect and groups is not None and sunk and need_p[base] and groups.takes(xin, dz, card):
-            groups.add(lambda: wgrad(idx, xin, dz, k, s, pad, scale, dbeta, collect=False), xin, dz, k, s, pad, scale, dbeta, (w, g, b, m, v),
-                       tuple(need_p[base:base + 3]))
+        sunk = all((not n) or _sink(t) is not None for n, t in zip(need, (w, g, b)))
+        if collect and groups is not None and sunk and need[0] and groups.takes(xin, dz, card):
+            groups.add(_Wgrad(lambda: wgrad(idx, xin, dz, k, s, pad, scale, dbeta, collect=False), xin, dz, k, s, pad, scale, dbeta,
+                              w, g, b, m, v, need[1], need[2]))
             return
-        if WGRAD_TRAIL and sunk:
-            trail = _Trail(dev, xin, dz, scale, dbeta)
-            trail.__enter__()
-        try:
-            _wgrad_body(idx, xin, dz, k, s, pad, scale, dbeta, w, g, b, m, v, base, wk, card)
-        finally:
-            if trail is not None:
-                trail.__exit__(None, None, None)
-
-    def _wgrad_body(idx, xin, dz, k, s, pad, scale, dbeta, w, g, b, m, v, base, wk, card=1):
-        part, S = K.conv_wgrad_partials([xin], [dz], k, s, pad, cardinality=card)
-        rowdot = K.zeros_f32(scale.numel(), scale.device) if need_p[base + 1] else None
-        grads[5 * idx] = _emit_wgrad(w, part, S, wk, scale, rowdot)
-        if need_p[base + 1]:
-            # a replicated [copies, C] accumulator is folded here; the fold lands in d beta's flat slot (zero at
-            # this point) or in a new tensor
-            rep = dbeta.dim() == 2
-            bs_fold = (_sink(b) if need_p[base + 2] else None) if rep else None
-            fold = None if not rep else (bs_fold if bs_fold is not None else torch.empty_like(dbeta[0]))
-            gs = _sink(g)
-            if gs is not None:                      # the slot is zero: plain store == accumulation
-                K.bn_dgamma(rowdot, dbeta, m, v, eps, out=gs, dbeta_out=fold)
-                _sunk(g)
-            else:
-                grads[5 * idx + 1] = K.bn_dgamma(rowdot, dbeta, m, v, eps, dbeta_out=fold)
-            if rep:
-                dbeta = fold
-        elif dbeta.dim() == 2:
-            dbeta = dbeta.sum(0)
-        if need_p[base + 2]:
-            bs = _sink(b)
-            if bs is None:
-                grads[5 * idx + 2] = dbeta
-            else:
-                if dbeta.data_ptr() != bs.data_ptr():   # (the projection shortcut shares conv3's column sums)
-                    bs.add_(dbeta)
-                _sunk(b)
+        # (rowdot, the fold of a replicated d beta and a dW without a slot are allocated INSIDE the scope: the trailing stream's own)
+        with (_Trail(dev, xin, dz, scale, dbeta) if WGRAD_TRAIL and sunk else _contextlib.nullcontext()):
+            part, S = K.conv_wgrad_partials([xin], [dz], k, s, pad, cardinality=card)
+            rowdot = K.zeros_f32(scale.numel(), scale.device) if need[1] else None
+            grads[base] = _emit_wgrad(w, part, S, wk, scale, rowdot)
+            grads[base + 1], grads[base + 2] = _emit_bn_grads(rowdot, dbeta, m, v, eps, need[1], need[2], g, b)
 
     wgrad(2, o2, dz3, 1, 1, 0, s3, db3)
     dz2 = torch.empty_like(o2)
@@ -671,9 +659,9 @@ def _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_p, need_x, stride, e
 
 
 class ResLayerFn(Function):
-    """A whole ResNet stage (res_layer.py:57-63: one projection block + identity blocks) as ONE autograd node.  Forward: the
-    launches of the blocks' BottleneckFn, one after the other.  Backward: the blocks' hand-scheduled backward passes chained
-    directly -- the gradient a block hands to its predecessor is produced by ONE input-gradient launch that already carries
+    """A whole ResNet stage (res_layer.py:57-63: one projection block + identity blocks) as ONE autograd node; a lone block
+    (modules.Bottleneck on its own) is a stage of one.  Forward: the blocks' launches (_bottleneck_forward), one after the
+    other.  Backward: the blocks' hand-scheduled backward passes (_bottleneck_backward) chained directly -- the gradient a block hands to its predecessor is produced by ONE input-gradient launch that already carries
     the predecessor's output-ReLU mask and the column sums for its d beta, so only the LAST block of the stage (whose output
     also leaves the stage) runs a stand-alone ReLU backward: 3 instead of 13 such passes per step for ResNet-50, and 3 autograd
     nodes instead of 13."""
@@ -681,37 +669,12 @@ class ResLayerFn(Function):
     @staticmethod
     def forward(ctx, x, strides, eps: float, counts, *params):
         K.RECORDED = any(ctx.needs_input_grad)      # see kernels.WINO_TRAIN_FWD
-        dev = x.device
-        blocks, off = [], 0
-        for n in counts:                             # parameters per block: 15 (identity shortcut) or 20 (projection)
-            blocks.append(params[off:off + n])
+        saved, meta, off, h = [], [], 0, x
+        for n, stride in zip(counts, strides):       # parameters per block: 15 (identity shortcut) or 20 (projection)
+            meta.append((stride, off, len(saved)))
+            saved += _bottleneck_forward(h, params[off:off + n], stride, eps)
+            h = saved[meta[-1][2] + 3]
             off += n
-        saved, meta = [], []
-
-        def cba(inp, prm, k, s, pad, res, relu):
-            w, g, b, m, v = prm
-            wk = ohwi(w)
-            scale, shift = _bn_fold_cached(g, b, m, v, eps)
-            N, H, W_, _ = inp.shape
-            out = torch.empty((N, K.conv_out_size(H, k, s, pad), K.conv_out_size(W_, k, s, pad), wk.shape[0]),
-                              dtype=inp.dtype, device=dev)
-            K.conv_forward([inp], wk, [out], k, s, pad, scale=scale, shift=shift,
-                           res=None if res is None else [res], relu=relu)
-            return out, scale
-
-        h = x
-        for bp, stride in zip(blocks, strides):
-            has_down = len(bp) == 20
-            P = [bp[5 * i:5 * i + 5] for i in range(4 if has_down else 3)]
-            o1, s1 = cba(h, P[0], 1, 1, 0, None, True)
-            o2, s2 = cba(o1, P[1], 3, stride, 1, None, True)
-            sd, idn = None, h
-            if has_down:
-                idn, sd = cba(h, P[3], 1, stride, 0, None, False)
-            y, s3 = cba(o2, P[2], 1, 1, 0, idn, True)
-            meta.append((stride, has_down, len(saved)))
-            saved += [h, o1, o2, y, s1, s2, s3] + ([sd] if has_down else [])
-            h = y
         ctx.meta, ctx.eps, ctx.counts, ctx.nsaved = meta, eps, counts, len(saved)
         ctx.save_for_backward(*saved, *params)
         return h
@@ -721,44 +684,31 @@ class ResLayerFn(Function):
         saved = ctx.saved_tensors
         acts, params = saved[:ctx.nsaved], saved[ctx.nsaved:]
         need = ctx.needs_input_grad
-        blocks, need_b, off = [], [], 0
-        for n in ctx.counts:
-            blocks.append(params[off:off + n])
-            need_b.append(list(need[4 + off:4 + off + n]))
-            off += n
         grads_all = [None] * len(params)
-        nb = len(blocks)
-        dz3 = db3 = None
+        nb = len(ctx.counts)
+        need_of = lambda i: list(need[4 + ctx.meta[i][1]:4 + ctx.meta[i][1] + ctx.counts[i]])
+        beta3_of = lambda i: params[ctx.meta[i][1] + 5 * 2 + 2]
+        # (a lone block launches its weight gradients as it goes: the collector would hold every single-member key back until flush())
+        groups = _WgradGroups(dy.device, ctx.eps) if WGRAD_GROUPED and nb > 1 else None
+        # the stage's output gradient arrives from outside: the one stand-alone ReLU backward
+        dz3, db3 = _exit_relu_backward(acts[ctx.meta[-1][2] + 3], dy.contiguous(), beta3_of(nb - 1), need_of(nb - 1)[5 * 2 + 2])
         dx = None
-        groups = _WgradGroups(dy.device, ctx.eps) if WGRAD_GROUPED else None
         for i in range(nb - 1, -1, -1):
-            stride, has_down, a0 = ctx.meta[i]
-            x, o1, o2, y, s1, s2, s3 = acts[a0:a0 + 7]
+            stride, off, a0 = ctx.meta[i]
+            has_down = ctx.counts[i] == 20
+            x, o1, o2, _, s1, s2, s3 = acts[a0:a0 + 7]
             sd = acts[a0 + 7] if has_down else None
-            bp = blocks[i]
-            P = [bp[5 * j:5 * j + 5] for j in range(4 if has_down else 3)]
-            if i == nb - 1:       # the stage's output gradient arrives from outside: the one stand-alone ReLU backward
-                b3 = P[2][2]
-                s_ = _sink(b3) if need_b[i][5 * 2 + 2] else None
-                dz3, db3 = K.relu_bwd_colsum(y, dy.contiguous(), True,
-                                             colsum_into=s_ if s_ is not None else K.zeros_f32(y.shape[3], x.device))
             # block i hands block i-1 its dz3 directly when block i has an identity shortcut (x IS block i-1's ReLU output)
             fuse = i > 0 and not has_down
-            need_x = need[0] if i == 0 else True
-            out, g = _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, P, need_b[i], need_x, stride, ctx.eps, dz3, db3,
-                                          out_mask=x if fuse else None, groups=groups)
-            base = sum(ctx.counts[:i])
-            grads_all[base:base + len(g)] = g
+            out, g = _bottleneck_backward(x, o1, o2, s1, s2, s3, sd, _per_conv(params[off:off + ctx.counts[i]]), need_of(i),
+                                          need[0] if i == 0 else True, stride, ctx.eps, dz3, db3, out_mask=x if fuse else None, groups=groups)
+            grads_all[off:off + len(g)] = g
             if i == 0:
                 dx = out
             elif fuse:
                 dz3, db3 = out
             else:                  # (a projection block in the middle of a stage: not a ResNet layout, kept general)
-                prev_y = acts[ctx.meta[i - 1][2] + 3]
-                pb3 = blocks[i - 1][5 * 2 + 2]
-                s_ = _sink(pb3) if need_b[i - 1][5 * 2 + 2] else None
-                dz3, db3 = K.relu_bwd_colsum(prev_y, out, True,
-                                             colsum_into=s_ if s_ is not None else K.zeros_f32(prev_y.shape[3], x.device))
+                dz3, db3 = _exit_relu_backward(x, out, beta3_of(i - 1), need_of(i - 1)[5 * 2 + 2])
         if groups is not None:
             groups.flush()
             ResLayerFn.last_group_launches = groups.launches
@@ -959,46 +909,21 @@ class HeadConvBias(Function):
         sizes = ctx.sizes
         dy = dy.contiguous()
         wk = ohwi(w)
-        if wk.shape[0] % 4:
-            return HeadConvBias._backward_padded(ctx, x_cat, w, wk, dy, sizes)
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
         dW = db = dx = None
+        if wk.shape[0] % 4:      # a 70- or 50-class gfl_cls
+            dx = torch.empty_like(x_cat) if need_x else None
+            dW, db = _padded_cout_backward(w, ctx.bias_param, dy, lambda t: K.level_views(t, sizes), K.level_views(x_cat, sizes),
+                                           K.level_views(dx, sizes) if need_x else None, 1, need_w, need_b)
+            return dx, dW, db, None
         xv, dv = K.level_views(x_cat, sizes), K.level_views(dy, sizes)
-        if ctx.needs_input_grad[1]:
+        if need_w:
             dW = _wgrad_plain(w, xv, dv, 3, 1, 1, keep=(x_cat, dy), trail=HEAD_TRAIL)
-        if ctx.needs_input_grad[2]:
+        if need_b:
             db = _bias_grad(ctx.bias_param, dy)
-        if ctx.needs_input_grad[0]:
+        if need_x:
             dx = torch.empty_like(x_cat)
             K.conv_dgrad(dv, K.weight_transpose(wk), K.level_views(dx, sizes), 3, 1, 1)
-        return dx, dW, db, None
-
-    @staticmethod
-    def _backward_padded(ctx, x_cat, w, wk, dy, sizes):
-        """Cout % 4 != 0 (a 70- or 50-class gfl_cls): both gradients contract over Cout, which the GEMM kernels take in
-        4-channel groups.  They run at Cp = round_up(Cout, 16) -- the 80-class head's launches for 70 classes -- on
-        zero-padded copies of dy and of the weight; the padding channels contribute exact zeros.  The weight gradient
-        reduces only rows [0, Cout) of the [S, Cp, 9 * Cin] partial slabs; the bias gradient is the column sum over Cout."""
-        Cout = wk.shape[0]
-        Cp = (Cout + 15) // 16 * 16
-        dyp = K.pad_channels(dy, Cp)
-        dvp = K.level_views(dyp, sizes)
-        dW = db = dx = None
-        if ctx.needs_input_grad[1]:
-            part, S = K.conv_wgrad_partials(K.level_views(x_cat, sizes), dvp, 3, 1, 1)
-            sink = _sink(w)
-            if sink is not None:
-                K.wgrad_reduce_rows(part, S, Cp, ohwi(sink), True)
-                _sunk(w)
-            else:
-                dWk = torch.empty_like(wk)
-                K.wgrad_reduce_rows(part, S, Cp, dWk, False)
-                dW = _to_oihw(dWk)
-        if ctx.needs_input_grad[2]:
-            db = _bias_grad(ctx.bias_param, dy)
-        if ctx.needs_input_grad[0]:
-            wp = K.pad_channels(wk.reshape(1, -1), Cp * wk[0].numel()).view(Cp, *wk.shape[1:])
-            dx = torch.empty_like(x_cat)
-            K.conv_dgrad(dvp, K.weight_transpose(wp), K.level_views(dx, sizes), 3, 1, 1)
         return dx, dW, db, None
 
 

@@ -226,9 +226,9 @@ class Bottleneck(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:      # NHWC map
         if not self.with_dcn and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return Fn.BottleneckFn.apply(x, self.stride, self.bn1.eps, *self._params())
+            return _res_layer_node([self], x)
         out = self._cba(x, self.conv1, self.bn1, None, True)
-        if self.with_dcn:      # leaf nodes composed here: BottleneckFn / ResLayerFn stay the plain blocks' nodes
+        if self.with_dcn:      # leaf nodes composed here: ResLayerFn stays the plain blocks' node
             c2, b2 = self.conv2, self.bn2
             out = Fn.DeformConvBNAct.apply(out, c2.weight, c2.conv_offset.weight, c2.conv_offset.bias, b2.weight, b2.bias,
                                            b2.running_mean, b2.running_var, c2.stride, True, b2.eps)
@@ -238,6 +238,13 @@ class Bottleneck(nn.Module):
         if self.downsample is not None:
             identity = self._cba(x, self.downsample[0], self.downsample[1], None, False)
         return self._cba(out, self.conv3, self.bn3, identity, True)
+
+
+def _res_layer_node(blocks, h: Tensor) -> Tensor:
+    """plain (non-DCN) bottlenecks in sequence -- a stage, or one block on its own -- as ONE autograd node"""
+    params = [blk._params() for blk in blocks]
+    return Fn.ResLayerFn.apply(h, tuple(blk.stride for blk in blocks), blocks[0].bn1.eps, tuple(len(pp) for pp in params),
+                               *[t for pp in params for t in pp])
 
 
 @MODELS.register_module()
@@ -386,12 +393,7 @@ class ResNet(nn.Module):
                 if Fn.RES_LAYER_NODE and torch.is_grad_enabled() and not any(blk.with_dcn for blk in layer) and all(
                         any(p.requires_grad for p in blk.parameters()) for blk in layer):
                     # the stage as ONE autograd node: its backward hands each block's dz3 straight to the block before it
-                    params, counts = [], []
-                    for blk in layer:
-                        pp = blk._params()
-                        params += pp
-                        counts.append(len(pp))
-                    h = Fn.ResLayerFn.apply(h, tuple(blk.stride for blk in layer), layer[0].bn1.eps, tuple(counts), *params)
+                    h = _res_layer_node(layer, h)
                 else:
                     for blk in layer:
                         h = blk(h)

@@ -119,7 +119,7 @@ def test_conv_dgrad_bf16_maps_with_mask_and_colsum(K, bf16_mode, N, Cin, Cout, H
     dx = torch.zeros((N, H, W, Cin), device="cuda", dtype=torch.bfloat16)
     K.conv_dgrad([nhwc_b(dy)], wt, [dx], k, s, p)
     close_bf16(to_nchw(dx), xr)
-    if s == 1:      # fused ReLU mask of the producer + d beta column sums (BottleneckFn.backward)
+    if s == 1:      # fused ReLU mask of the producer + d beta column sums (functional._bottleneck_backward)
         fwd = _r(G.randn(14, N, Cin, H, W))
         dx2 = torch.empty_like(dx)
         cs = torch.zeros(Cin, device="cuda")
