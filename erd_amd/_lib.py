@@ -157,7 +157,10 @@ _SIGNATURES = {
     "erd_gfl_losses_fwd": [P, P, P, P, P, P, C.POINTER(i64), C.POINTER(i32), i32, i32, i64, i32, i32, P, P, P, P],
     "erd_gfl_losses_bwd": [P, P, P, P, P, P, C.POINTER(i64), C.POINTER(i32), i32, i32, i64, i32, i32, P, P, P, P,
                            P, P],
-    "erd_l2_distill": [P, P, P, P, i32, i64, i32, i32, i32, P, P],
+    "erd_gfl_losses_fwd_box": [P, P, P, P, P, P, C.POINTER(i64), C.POINTER(i32), i32, i32, i64, i32, i32, P, P, P, i32, f32, P],
+    "erd_gfl_losses_bwd_box": [P, P, P, P, P, P, C.POINTER(i64), C.POINTER(i32), i32, i32, i64, i32, i32, P, P, P, P,
+                               P, i32, f32, P],
+    "erd_l2_distill":[P, P, P, P, i32, i64, i32, i32, i32, P, P],
     "erd_l2_distill_bwd": [P, P, P, P, P, i32, i64, i32, i32, i32, P, P],
     "erd_distill_nms": [P, P, P, P, P, i32, i64, i32, f32, P, P, P, C.c_size_t, P],
     "erd_kd_kl": [P, P, P, P, i32, i64, i32, i32, f32, P, P],
@@ -180,6 +183,7 @@ _SIGNATURES = {
     "erd_dfl": [P, P, P, i64, i32, P, P, P],
     "erd_kd_kl_rows": [P, P, P, i64, i32, f32, P, P, P],
     "erd_giou": [P, P, P, i64, f32, P, P, P],
+    "erd_iou_loss": [P, P, P, i64, i32, f32, P, P, P],
     "erd_bbox_overlaps": [P, P, i64, i64, i32, i32, f32, P, P],
     "erd_integral": [P, P, i64, i32, P, P, P],
     "erd_distance2bbox": [P, P, P, i64, f32, f32, P, P, P],

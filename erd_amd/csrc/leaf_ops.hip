@@ -9,11 +9,13 @@
 //   distribution_focal_loss       models/losses/gfocal_loss.py:143-165
 //   knowledge_distillation_kl_div models/losses/kd_loss.py:12-37
 //   giou_loss / bbox_overlaps     models/losses/iou_loss.py:110-126, structures/bbox/bbox_overlaps.py:13-199
+//   iou_loss / diou_loss / ciou_loss  models/losses/iou_loss.py:16-54, 130-181, 185-246
 //   Integral                      models/dense_heads/gfl_head.py:29-62
 //   distance2bbox / bbox2distance structures/bbox/transforms.py:147-230
 //   weight_reduce_loss            models/losses/utils.py:30-65
 //   AssignResult fields           models/task_modules/assigners/atss_assigner.py:238-254
 #include "erd_common.h"
+#include "erd_box_loss.h"
 
 namespace {
 
@@ -216,6 +218,22 @@ __global__ __launch_bounds__(256) void giou_kernel(const float4* __restrict__ pr
     dpred[i] = make_float4(g[0], g[1], g[2], g[3]);
 }
 
+// IoU / DIoU / CIoU loss rows and coef[i] * d row / d pred: the device functions of the fused step kernel (erd_box_loss.h)
+template <int KIND>
+__global__ __launch_bounds__(256) void iou_loss_kernel(const float4* __restrict__ pred, const float4* __restrict__ target,
+                                                       const float* __restrict__ coef, int64_t n, float eps,
+                                                       float* __restrict__ rows, float4* __restrict__ dpred) {
+    const int64_t i = blockIdx.x * 256ll + threadIdx.x;
+    if (i >= n) return;
+    float g[4];
+    const float v = erd::box::loss_grad<KIND>(pred[i], target[i], eps, dpred ? g : nullptr, nullptr);
+    if (rows) rows[i] = v;
+    if (dpred) {
+        const float c = coef[i];
+        dpred[i] = make_float4(c * g[0], c * g[1], c * g[2], c * g[3]);
+    }
+}
+
 // distance2bbox (decode): x1 = px - l, y1 = py - t, x2 = px + r, y2 = py + b (+ optional clamp to [0, W] x [0, H])
 __global__ __launch_bounds__(256) void d2b_kernel(const float2* __restrict__ pts, const float4* __restrict__ dist, int64_t n,
                                                   float max_h, float max_w, float4* __restrict__ out) {
@@ -365,6 +383,27 @@ extern "C" int erd_giou(const float* pred, const float* target, const float* coe
         hipLaunchKernelGGL(giou_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(pred),
                            reinterpret_cast<const float4*>(target), coef, n, eps, rows, reinterpret_cast<float4*>(dpred));
     return erd::check_launch("giou");
+}
+extern "C" int erd_iou_loss(const float* pred, const float* target, const float* coef, int64_t n, int kind, float eps, float* rows,
+                            float* dpred, erd_stream_t stream) {
+    ERD_REQUIRE(((pred && target && (rows || (dpred && coef))) || n == 0) && n >= 0, "iou_loss: bad args");
+    ERD_REQUIRE(kind >= ERD_BOX_IOU_LOG && kind <= ERD_BOX_CIOU && eps >= 0.f, "iou_loss: kind=%d eps=%g (GIoU is erd_giou)", kind,
+                (double)eps);
+    if (n > 0) {
+        const float4* p = reinterpret_cast<const float4*>(pred);
+        const float4* t = reinterpret_cast<const float4*>(target);
+        float4* d = reinterpret_cast<float4*>(dpred);
+        const dim3 grid(blocks_for(n)), block(256);
+        hipStream_t st = (hipStream_t)stream;
+        switch (kind) {
+            case ERD_BOX_IOU_LOG: hipLaunchKernelGGL(iou_loss_kernel<ERD_BOX_IOU_LOG>, grid, block, 0, st, p, t, coef, n, eps, rows, d); break;
+            case ERD_BOX_IOU_LINEAR: hipLaunchKernelGGL(iou_loss_kernel<ERD_BOX_IOU_LINEAR>, grid, block, 0, st, p, t, coef, n, eps, rows, d); break;
+            case ERD_BOX_IOU_SQUARE: hipLaunchKernelGGL(iou_loss_kernel<ERD_BOX_IOU_SQUARE>, grid, block, 0, st, p, t, coef, n, eps, rows, d); break;
+            case ERD_BOX_DIOU: hipLaunchKernelGGL(iou_loss_kernel<ERD_BOX_DIOU>, grid, block, 0, st, p, t, coef, n, eps, rows, d); break;
+            default: hipLaunchKernelGGL(iou_loss_kernel<ERD_BOX_CIOU>, grid, block, 0, st, p, t, coef, n, eps, rows, d); break;
+        }
+    }
+    return erd::check_launch("iou_loss");
 }
 extern "C" int erd_distance2bbox(const float* points, const float* dist, const float* dout, int64_t n, float max_h, float max_w,
                                  float* out, float* ddist, erd_stream_t stream) {

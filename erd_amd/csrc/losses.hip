@@ -4,6 +4,7 @@
 // reductions, f64 accumulation of the statistics that feed data-dependent decisions).
 // Built with -ffp-contract=off: index/mask decisions must not depend on FMA contraction.
 #include "erd_common.h"
+#include "erd_box_loss.h"
 #include <algorithm>
 
 namespace {
@@ -398,7 +399,9 @@ inline size_t gl_lds_bytes(const float* cls, int c_all) {
     return (GL_ROWS * (size_t)c_all + (aligned ? 0 : 3)) * sizeof(float);
 }
 
-template <bool BWD>
+// BOX: the head's loss_bbox (enum erd_box_loss).  Only the box term differs between the instantiations: ERD_BOX_GIOU runs
+// giou_loss_grad at its built-in eps, the other kinds erd::box::loss_grad<BOX> at `box_eps`; everything else is the same code.
+template <bool BWD, int BOX>
 __global__ __launch_bounds__(256) void gfl_losses_kernel(const float* __restrict__ cls, const float* __restrict__ bbox,
                                                           const float4* __restrict__ anchors,
                                                           const int64_t* __restrict__ labels,
@@ -407,7 +410,7 @@ __global__ __launch_bounds__(256) void gfl_losses_kernel(const float* __restrict
                                                           int c_old, int c_all, float* __restrict__ score_ws,
                                                           float* __restrict__ wt_ws, double* __restrict__ out_sums,
                                                           const float* __restrict__ coef, float* __restrict__ dcls,
-                                                          float* __restrict__ dbbox) {
+                                                          float* __restrict__ dbbox, float box_eps) {
     extern __shared__ __attribute__((aligned(16))) float sm_base[];  // [off + GL_ROWS * c_all] logits (then grads)
     const int n = blockIdx.y;
     const int64_t a0 = (int64_t)blockIdx.x * GL_ROWS;
@@ -463,7 +466,8 @@ __global__ __launch_bounds__(256) void gfl_losses_kernel(const float* __restrict
         const float4 bt = btargets[gi];
         const float4 tg = make_float4(bt.x / stride, bt.y / stride, bt.z / stride, bt.w / stride);
         float iou;
-        giou_l = giou_loss_grad(pred, tg, 1e-6f, BWD ? gd : nullptr, &iou);
+        if (BOX == ERD_BOX_GIOU) giou_l = giou_loss_grad(pred, tg, 1e-6f, BWD ? gd : nullptr, &iou);
+        else giou_l = erd::box::loss_grad<BOX == ERD_BOX_GIOU ? ERD_BOX_IOU_LOG : BOX>(pred, tg, box_eps, BWD ? gd : nullptr, &iou);
         score = iou;
         // bbox2distance(..., max_dis=16, eps=.1): clamp to [0, 15.9]
         const float raw = q == 0 ? cx - tg.x : (q == 1 ? cy - tg.y : (q == 2 ? tg.z - cx : tg.w - cy));
@@ -886,21 +890,77 @@ extern "C" int erd_atss_assign(const float* anchors, const uint8_t* valid, const
     return erd::check_launch("atss_assign");
 }
 
+namespace {
+template <bool BWD, int BOX>
+void launch_gfl_losses(hipStream_t st, const float* cls, const float* bbox, const float* anchors, const int64_t* labels,
+                       const float* label_weights, const float* bbox_targets, const Levels5& lv, int N, int64_t A, int c_old,
+                       int c_all, float* score_ws, float* wt_ws, double* out_sums, const float* coef, float* dcls, float* dbbox,
+                       float box_eps) {
+    hipLaunchKernelGGL((gfl_losses_kernel<BWD, BOX>), dim3((unsigned)((A + GL_ROWS - 1) / GL_ROWS), N), dim3(256),
+                       gl_lds_bytes(cls, c_all), st, cls, bbox, reinterpret_cast<const float4*>(anchors), labels,
+                       label_weights, reinterpret_cast<const float4*>(bbox_targets), lv, A, c_old, c_all, score_ws,
+                       wt_ws, out_sums, coef, dcls, dbbox, box_eps);
+}
+
+template <bool BWD, typename... Args>
+void launch_gfl_losses_kind(int box_loss, Args... args) {
+    switch (box_loss) {
+        case ERD_BOX_GIOU: launch_gfl_losses<BWD, ERD_BOX_GIOU>(args...); break;
+        case ERD_BOX_IOU_LOG: launch_gfl_losses<BWD, ERD_BOX_IOU_LOG>(args...); break;
+        case ERD_BOX_IOU_LINEAR: launch_gfl_losses<BWD, ERD_BOX_IOU_LINEAR>(args...); break;
+        case ERD_BOX_IOU_SQUARE: launch_gfl_losses<BWD, ERD_BOX_IOU_SQUARE>(args...); break;
+        case ERD_BOX_DIOU: launch_gfl_losses<BWD, ERD_BOX_DIOU>(args...); break;
+        default: launch_gfl_losses<BWD, ERD_BOX_CIOU>(args...); break;
+    }
+}
+
+// the GIoU instantiation is built at GIoULoss' default eps; the other kinds take the module's eps as an argument
+bool box_kind_ok(int box_loss, float box_eps) {
+    if (box_loss == ERD_BOX_GIOU) return box_eps == 1e-6f;
+    return box_loss >= ERD_BOX_IOU_LOG && box_loss <= ERD_BOX_CIOU && box_eps >= 0.f;
+}
+}  // namespace
+
+extern "C" int erd_gfl_losses_fwd_box(const float* cls, const float* bbox, const float* anchors, const int64_t* labels,
+                                      const float* label_weights, const float* bbox_targets, const int64_t* lvl_off,
+                                      const int* strides, int nlvl, int N, int64_t A, int c_old, int c_all,
+                                      float* score_ws, float* wt_ws, double* out_sums, int box_loss, float box_eps,
+                                      erd_stream_t stream) {
+    ERD_REQUIRE(cls && bbox && anchors && labels && label_weights && bbox_targets && lvl_off && strides && score_ws &&
+                    wt_ws && out_sums, "gfl_losses_fwd: null");
+    ERD_REQUIRE(c_all >= 1 && c_old >= 0 && c_old < c_all && nlvl <= ERD_MAX_SEG, "gfl_losses_fwd: channels");
+    ERD_REQUIRE(box_kind_ok(box_loss, box_eps), "gfl_losses_fwd: box_loss=%d box_eps=%g", box_loss, (double)box_eps);
+    hipStream_t st = (hipStream_t)stream;
+    const Levels5 lv = make_levels(lvl_off, strides, nlvl, nullptr, nullptr);
+    ERD_ZERO_ASYNC(out_sums, sizeof(double) * 4 * nlvl, st);
+    launch_gfl_losses_kind<false>(box_loss, st, cls, bbox, anchors, labels, label_weights, bbox_targets, lv, N, A, c_old, c_all,
+                                  score_ws, wt_ws, out_sums, (const float*)nullptr, (float*)nullptr, (float*)nullptr, box_eps);
+    return erd::check_launch("gfl_losses_fwd");
+}
+
+extern "C" int erd_gfl_losses_bwd_box(const float* cls, const float* bbox, const float* anchors, const int64_t* labels,
+                                      const float* label_weights, const float* bbox_targets, const int64_t* lvl_off,
+                                      const int* strides, int nlvl, int N, int64_t A, int c_old, int c_all,
+                                      const float* score_ws, const float* wt_ws, const float* coef, float* dcls,
+                                      float* dbbox, int box_loss, float box_eps, erd_stream_t stream) {
+    ERD_REQUIRE(cls && bbox && anchors && labels && label_weights && bbox_targets && lvl_off && strides && score_ws &&
+                    coef && dcls && dbbox, "gfl_losses_bwd: null");
+    ERD_REQUIRE(c_all >= 1 && c_old >= 0 && c_old < c_all && nlvl <= ERD_MAX_SEG, "gfl_losses_bwd: channels");
+    ERD_REQUIRE(box_kind_ok(box_loss, box_eps), "gfl_losses_bwd: box_loss=%d box_eps=%g", box_loss, (double)box_eps);
+    const Levels5 lv = make_levels(lvl_off, strides, nlvl, nullptr, nullptr);
+    launch_gfl_losses_kind<true>(box_loss, (hipStream_t)stream, cls, bbox, anchors, labels, label_weights, bbox_targets, lv, N, A,
+                                 c_old, c_all, const_cast<float*>(score_ws), const_cast<float*>(wt_ws), (double*)nullptr, coef,
+                                 dcls, dbbox, box_eps);
+    return erd::check_launch("gfl_losses_bwd");
+}
+
+// GIoULoss, the head's default: the ERD_BOX_GIOU instantiation
 extern "C" int erd_gfl_losses_fwd(const float* cls, const float* bbox, const float* anchors, const int64_t* labels,
                                   const float* label_weights, const float* bbox_targets, const int64_t* lvl_off,
                                   const int* strides, int nlvl, int N, int64_t A, int c_old, int c_all,
                                   float* score_ws, float* wt_ws, double* out_sums, erd_stream_t stream) {
-    ERD_REQUIRE(cls && bbox && anchors && labels && label_weights && bbox_targets && lvl_off && strides && score_ws &&
-                    wt_ws && out_sums, "gfl_losses_fwd: null");
-    ERD_REQUIRE(c_all >= 1 && c_old >= 0 && c_old < c_all && nlvl <= ERD_MAX_SEG, "gfl_losses_fwd: channels");
-    hipStream_t st = (hipStream_t)stream;
-    const Levels5 lv = make_levels(lvl_off, strides, nlvl, nullptr, nullptr);
-    ERD_ZERO_ASYNC(out_sums, sizeof(double) * 4 * nlvl, st);
-    hipLaunchKernelGGL(gfl_losses_kernel<false>, dim3((unsigned)((A + GL_ROWS - 1) / GL_ROWS), N), dim3(256),
-                       gl_lds_bytes(cls, c_all), st, cls, bbox, reinterpret_cast<const float4*>(anchors), labels,
-                       label_weights, reinterpret_cast<const float4*>(bbox_targets), lv, A, c_old, c_all, score_ws,
-                       wt_ws, out_sums, nullptr, nullptr, nullptr);
-    return erd::check_launch("gfl_losses_fwd");
+    return erd_gfl_losses_fwd_box(cls, bbox, anchors, labels, label_weights, bbox_targets, lvl_off, strides, nlvl, N, A, c_old,
+                                  c_all, score_ws, wt_ws, out_sums, ERD_BOX_GIOU, 1e-6f, stream);
 }
 
 extern "C" int erd_gfl_losses_bwd(const float* cls, const float* bbox, const float* anchors, const int64_t* labels,
@@ -908,16 +968,8 @@ extern "C" int erd_gfl_losses_bwd(const float* cls, const float* bbox, const flo
                                   const int* strides, int nlvl, int N, int64_t A, int c_old, int c_all,
                                   const float* score_ws, const float* wt_ws, const float* coef, float* dcls,
                                   float* dbbox, erd_stream_t stream) {
-    ERD_REQUIRE(cls && bbox && anchors && labels && label_weights && bbox_targets && lvl_off && strides && score_ws &&
-                    coef && dcls && dbbox, "gfl_losses_bwd: null");
-    ERD_REQUIRE(c_all >= 1 && c_old >= 0 && c_old < c_all && nlvl <= ERD_MAX_SEG, "gfl_losses_bwd: channels");
-    const Levels5 lv = make_levels(lvl_off, strides, nlvl, nullptr, nullptr);
-    hipLaunchKernelGGL(gfl_losses_kernel<true>, dim3((unsigned)((A + GL_ROWS - 1) / GL_ROWS), N), dim3(256),
-                       gl_lds_bytes(cls, c_all), (hipStream_t)stream, cls, bbox,
-                       reinterpret_cast<const float4*>(anchors), labels, label_weights,
-                       reinterpret_cast<const float4*>(bbox_targets), lv, A, c_old, c_all,
-                       const_cast<float*>(score_ws), const_cast<float*>(wt_ws), nullptr, coef, dcls, dbbox);
-    return erd::check_launch("gfl_losses_bwd");
+    return erd_gfl_losses_bwd_box(cls, bbox, anchors, labels, label_weights, bbox_targets, lvl_off, strides, nlvl, N, A, c_old,
+                                  c_all, score_ws, wt_ws, coef, dcls, dbbox, ERD_BOX_GIOU, 1e-6f, stream);
 }
 
 extern "C" int erd_l2_distill(const float* s_cls, const float* t_cls, const int64_t* idx_cls, const int32_t* counts,

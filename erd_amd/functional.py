@@ -948,14 +948,14 @@ class ERDLossFn(Function):
     """All loss entries of the step as ONE vector
         [loss_cls(L) | loss_bbox(L) | loss_dfl(L) | loss_dist_cls(N) | loss_dist_bbox(N)]
     (gfl_head_increment_erd.py:334-454).  `t` carries the no-grad side: targets, teacher outputs, ERS lists,
-    NMS keep mask (None for the plain GFL head loss)."""
+    NMS keep mask (None for the plain GFL head loss), and `box_loss` = (kind, eps) of the head's loss_bbox (absent: GIoU)."""
 
     @staticmethod
     def forward(ctx, s_cls, s_bbox, t):
         N, A, c_all = s_cls.shape
         L = len(t.sizes)
         score, wt, sums = K.gfl_losses_fwd(s_cls, s_bbox, t.anchors, t.labels, t.label_weights, t.bbox_targets,
-                                           t.sizes, t.strides, t.c_old, c_all)
+                                           t.sizes, t.strides, t.c_old, c_all, getattr(t, "box_loss", K.BOX_LOSS_GIOU))
         avg = K.loss_avg(t.num_pos, sums)
         if t.world_size > 1:       # reduce_mean x2 (dist_utils.py:59-65) fused into one 2-float all-reduce
             from .dist_utils import reduce_mean
@@ -984,7 +984,7 @@ class ERDLossFn(Function):
                                   t.ers["counts"] if nd else None, L, nd, t.c_old, t.dist_loss_weight, t.lw_cls,
                                   t.lw_bbox, t.lw_dfl, t.lw_ld, dlosses.contiguous(), False, True)
         dcls, dbbox = K.gfl_losses_bwd(s_cls, s_bbox, t.anchors, t.labels, t.label_weights, t.bbox_targets, t.sizes,
-                                       t.strides, t.c_old, c_all, score, wt, coef)
+                                       t.strides, t.c_old, c_all, score, wt, coef, getattr(t, "box_loss", K.BOX_LOSS_GIOU))
         if nd:
             K.l2_distill_bwd_(s_cls, t.t_cls, t.ers["idx_cls"], t.ers["counts"], coef[4 * L:], t.c_old, dcls)
             K.kd_kl_bwd_(s_bbox, t.t_bbox, s_cls, t.keep, coef[4 * L + N:], t.c_old, t.T, dbbox)

@@ -1784,23 +1784,42 @@ def atss_assign(anchors: Tensor, valid: Optional[Tensor], sizes, gt_boxes: Tenso
     return labels, lw, bt, npos
 
 
-def gfl_losses_fwd(cls, bbox, anchors, labels, lw, bt, sizes, strides, c_old, c_all):
+# enum erd_box_loss (include/erd_hip.h): the head's loss_bbox as the fused loss kernels know it
+BOX_GIOU, BOX_IOU_LOG, BOX_IOU_LINEAR, BOX_IOU_SQUARE, BOX_DIOU, BOX_CIOU = range(6)
+BOX_LOSS_GIOU = (BOX_GIOU, 1e-6)
+
+
+def gfl_losses_fwd(cls, bbox, anchors, labels, lw, bt, sizes, strides, c_old, c_all, box_loss=BOX_LOSS_GIOU):
+    """`box_loss` = (kind, eps).  GIoU goes through the entry it always had; the other kinds through erd_gfl_losses_fwd_box."""
     N, A, _ = cls.shape
     dev = cls.device
     score = torch.empty((N, A), dtype=torch.float32, device=dev)
     wt = torch.empty((N, A), dtype=torch.float32, device=dev)
     sums = torch.empty((len(sizes), 4), dtype=torch.float64, device=dev)
-    call("erd_gfl_losses_fwd", _p(cls), _p(bbox), _p(anchors), _p(labels), _p(lw), _p(bt), _lvl_off(sizes),
-         _iarr(strides), len(sizes), N, A, c_old, c_all, _p(score), _p(wt), _p(sums), _stream())
+    kind, eps = box_loss
+    if kind == BOX_GIOU:
+        if eps != 1e-6:
+            raise NotImplementedError("GIoULoss(eps != 1e-6): the fused step kernels use the module default")
+        call("erd_gfl_losses_fwd", _p(cls), _p(bbox), _p(anchors), _p(labels), _p(lw), _p(bt), _lvl_off(sizes),
+             _iarr(strides), len(sizes), N, A, c_old, c_all, _p(score), _p(wt), _p(sums), _stream())
+    else:
+        call("erd_gfl_losses_fwd_box", _p(cls), _p(bbox), _p(anchors), _p(labels), _p(lw), _p(bt), _lvl_off(sizes),
+             _iarr(strides), len(sizes), N, A, c_old, c_all, _p(score), _p(wt), _p(sums), int(kind), float(eps), _stream())
     return score, wt, sums
 
 
-def gfl_losses_bwd(cls, bbox, anchors, labels, lw, bt, sizes, strides, c_old, c_all, score, wt, coef):
+def gfl_losses_bwd(cls, bbox, anchors, labels, lw, bt, sizes, strides, c_old, c_all, score, wt, coef, box_loss=BOX_LOSS_GIOU):
     N, A, _ = cls.shape
     dcls = torch.empty_like(cls)
     dbbox = torch.empty_like(bbox)
-    call("erd_gfl_losses_bwd", _p(cls), _p(bbox), _p(anchors), _p(labels), _p(lw), _p(bt), _lvl_off(sizes),
-         _iarr(strides), len(sizes), N, A, c_old, c_all, _p(score), _p(wt), _p(coef), _p(dcls), _p(dbbox), _stream())
+    kind, eps = box_loss
+    if kind == BOX_GIOU:
+        call("erd_gfl_losses_bwd", _p(cls), _p(bbox), _p(anchors), _p(labels), _p(lw), _p(bt), _lvl_off(sizes),
+             _iarr(strides), len(sizes), N, A, c_old, c_all, _p(score), _p(wt), _p(coef), _p(dcls), _p(dbbox), _stream())
+    else:
+        call("erd_gfl_losses_bwd_box", _p(cls), _p(bbox), _p(anchors), _p(labels), _p(lw), _p(bt), _lvl_off(sizes),
+             _iarr(strides), len(sizes), N, A, c_old, c_all, _p(score), _p(wt), _p(coef), _p(dcls), _p(dbbox), int(kind),
+             float(eps), _stream())
     return dcls, dbbox
 
 

@@ -181,6 +181,63 @@ def giou_loss(pred: Tensor, target: Tensor, weight=None, eps: float = 1e-6, redu
     return _row_loss(pred, weight, reduction, avg_factor, loss_weight, (_giou_rows, _giou_bwd), _f32c(target.detach()), float(eps))
 
 
+# ---- IoU / DIoU / CIoU (iou_loss.py:16-54, 130-181, 185-246; modules :307-389, 532-599, 603-670) ------------------------
+IOU_MODES = {"log": K.BOX_IOU_LOG, "linear": K.BOX_IOU_LINEAR, "square": K.BOX_IOU_SQUARE}
+
+
+def _iou_rows(pred, fixed):
+    target, kind, eps = fixed
+    rows = torch.empty(pred.shape[0], dtype=torch.float32, device=pred.device)
+    call("erd_iou_loss", _p(pred), _p(target), None, pred.shape[0], kind, eps, _p(rows), None, _stream())
+    return rows
+
+
+def _iou_bwd(pred, fixed, coef):
+    target, kind, eps = fixed
+    d = torch.empty_like(pred)
+    call("erd_iou_loss", _p(pred), _p(target), _p(coef), pred.shape[0], kind, eps, None, _p(d), _stream())
+    return d
+
+
+def _zero_weight_sum(pred: Tensor, weight: Tensor) -> Tensor:
+    """the modules' early return `(pred * weight).sum()` (iou_loss.py:369-373, 578-581, 650-653): a weighted sum over the
+    coordinates, its backward the weights themselves"""
+    if pred.dim() == weight.dim() + 1:
+        weight = weight.unsqueeze(1)
+    w = _f32c(weight.expand_as(pred)).reshape(-1)
+    return _row_loss(pred.reshape(-1), w, "sum", None, 1.0, (lambda p, fixed: p, lambda p, fixed, coef: coef))
+
+
+def _box_loss(kind: int, early_out_on_none: bool, pred, target, weight, eps, reduction, avg_factor, loss_weight) -> Tensor:
+    K._require_gpu(pred, target)
+    if weight is not None and (early_out_on_none or reduction != "none") and not bool(torch.any(weight > 0)):
+        return _zero_weight_sum(_f32c(pred), weight)
+    if weight is not None and weight.dim() > 1:       # per-coordinate weights -> per-box mean
+        if weight.shape != pred.shape:
+            raise AssertionError
+        weight = weight.mean(-1)
+    return _row_loss(pred, weight, reduction, avg_factor, loss_weight, (_iou_rows, _iou_bwd), _f32c(target.detach()), int(kind),
+                     float(eps))
+
+
+def iou_loss(pred: Tensor, target: Tensor, weight=None, mode: str = "log", eps: float = 1e-6, reduction="mean", avg_factor=None,
+             loss_weight: float = 1.0) -> Tensor:
+    """IoULoss.forward: -log / 1 - / 1 - ^2 of bbox_overlaps(pred, target).clamp(min=eps).  The all-zero-weight early return
+    applies only when the reduction is not 'none' (iou_loss.py:369-370)."""
+    return _box_loss(IOU_MODES[mode], False, pred, target, weight, eps, reduction, avg_factor, loss_weight)
+
+
+def diou_loss(pred: Tensor, target: Tensor, weight=None, eps: float = 1e-6, reduction="mean", avg_factor=None,
+              loss_weight: float = 1.0) -> Tensor:
+    return _box_loss(K.BOX_DIOU, True, pred, target, weight, eps, reduction, avg_factor, loss_weight)
+
+
+def ciou_loss(pred: Tensor, target: Tensor, weight=None, eps: float = 1e-6, reduction="mean", avg_factor=None,
+              loss_weight: float = 1.0) -> Tensor:
+    """Where the reference's own fp32 value is not finite (two identical boxes: alpha = 0 / 0), the row is not finite here"""
+    return _box_loss(K.BOX_CIOU, True, pred, target, weight, eps, reduction, avg_factor, loss_weight)
+
+
 def bbox_overlaps(bboxes1: Tensor, bboxes2: Tensor, mode: str = "iou", is_aligned: bool = False, eps: float = 1e-6) -> Tensor:
     """structures/bbox/bbox_overlaps.py:13-199 for 2-D [m,4] / [n,4] inputs (a trailing score column is ignored)"""
     if mode not in ("iou", "giou"):

@@ -16,6 +16,7 @@ from __future__ import annotations
 import math
 import os
 import sys
+import warnings
 from collections import OrderedDict
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Tuple, Union
@@ -698,6 +699,62 @@ class GIoULoss(_LossCfg):
 
 
 @MODELS.register_module()
+class IoULoss(_LossCfg):
+    def __init__(self, linear=False, eps=1e-6, reduction="mean", loss_weight=1.0, mode="log"):
+        super().__init__()
+        assert mode in ["linear", "square", "log"]
+        if linear:
+            mode = "linear"
+            warnings.warn('DeprecationWarning: Setting "linear=True" in IOULoss is deprecated, please use "mode=`linear`" instead.')
+        self.mode, self.linear, self.eps, self.reduction, self.loss_weight = mode, linear, eps, reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, **kwargs):
+        """losses/iou_loss.py:341-389: pred / target [n, 4] xyxy"""
+        from . import leaf
+        return leaf.iou_loss(pred, target, weight, self.mode, self.eps, self._reduction(reduction_override), avg_factor,
+                             self.loss_weight)
+
+
+@MODELS.register_module()
+class DIoULoss(_LossCfg):
+    def __init__(self, eps=1e-6, reduction="mean", loss_weight=1.0):
+        super().__init__()
+        self.eps, self.loss_weight, self.reduction = eps, loss_weight, reduction
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, **kwargs):
+        """losses/iou_loss.py:553-599"""
+        from . import leaf
+        return leaf.diou_loss(pred, target, weight, self.eps, self._reduction(reduction_override), avg_factor, self.loss_weight)
+
+
+@MODELS.register_module()
+class CIoULoss(_LossCfg):
+    def __init__(self, eps=1e-6, reduction="mean", loss_weight=1.0):
+        super().__init__()
+        self.eps, self.loss_weight, self.reduction = eps, loss_weight, reduction
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, **kwargs):
+        """losses/iou_loss.py:625-671"""
+        from . import leaf
+        return leaf.ciou_loss(pred, target, weight, self.eps, self._reduction(reduction_override), avg_factor, self.loss_weight)
+
+
+def box_loss_kind(loss_bbox) -> Tuple[int, float]:
+    """(enum erd_box_loss, eps) of a head's loss_bbox module for the fused loss kernels of the training step"""
+    if isinstance(loss_bbox, GIoULoss):
+        if loss_bbox.eps != 1e-6:
+            raise NotImplementedError("GIoULoss(eps != 1e-6) in a GFL head: the fused step kernels use the module default")
+        return K.BOX_LOSS_GIOU
+    if isinstance(loss_bbox, IoULoss):
+        from . import leaf
+        return leaf.IOU_MODES[loss_bbox.mode], float(loss_bbox.eps)
+    if isinstance(loss_bbox, (DIoULoss, CIoULoss)):
+        return (K.BOX_DIOU if isinstance(loss_bbox, DIoULoss) else K.BOX_CIOU), float(loss_bbox.eps)
+    raise NotImplementedError(f"loss_bbox={type(loss_bbox).__name__} in a GFL head: the fused step kernels are built for "
+                              "GIoULoss, IoULoss, DIoULoss and CIoULoss")
+
+
+@MODELS.register_module()
 class KnowledgeDistillationKLDivLoss(_LossCfg):
     def __init__(self, reduction="mean", loss_weight=1.0, T=10):
         super().__init__()
@@ -768,8 +825,7 @@ class GFLHead(nn.Module):
         for m in (self.loss_cls, self.loss_bbox, self.loss_dfl):
             if getattr(m, "reduction", "mean") != "mean":
                 raise NotImplementedError(f"{type(m).__name__}(reduction={m.reduction!r}) in a GFL head: the fused step kernels use 'mean'")
-        if getattr(self.loss_bbox, "eps", 1e-6) != 1e-6:
-            raise NotImplementedError("GIoULoss(eps != 1e-6) in a GFL head: the fused step kernels use the module default")
+        self._box_loss = box_loss_kind(self.loss_bbox)     # (kind, eps) of the fused loss launches; refuses what is not built
         if train_cfg:
             self.assigner = TASK_UTILS.build(train_cfg["assigner"])
             if train_cfg.get("allowed_border", -1) >= 0 or train_cfg.get("pos_weight", -1) > 0:
@@ -932,6 +988,7 @@ class GFLHead(nn.Module):
     def _loss_vector(self, s_cls, s_bbox, t: SimpleNamespace) -> Tensor:
         t.lw_cls, t.lw_bbox, t.lw_dfl = self.loss_cls.loss_weight, self.loss_bbox.loss_weight, self.loss_dfl.loss_weight
         t.world_size = _world_size()
+        t.box_loss = self._box_loss
         return Fn.ERDLossFn.apply(s_cls, s_bbox, t)
 
     def loss_by_feat_cat(self, s_cls, s_bbox, sizes, batch_gt_instances, batch_img_metas) -> dict:

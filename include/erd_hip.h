@@ -555,6 +555,31 @@ int erd_gfl_losses_bwd(const float* cls, const float* bbox, const float* anchors
                        const int* strides, int nlvl, int N, int64_t A, int c_old, int c_all,
                        const float* score_ws, const float* wt_ws, const float* coef /* erd_loss_finalize layout */,
                        float* dcls, float* dbbox, erd_stream_t stream);
+/* The same two launches with the head's `loss_bbox` chosen: box_loss is one of enum erd_box_loss, box_eps the module's `eps`
+ * (IoULoss: the clamp of the IoU, iou_loss.py:45; DIoULoss / CIoULoss: added to the union, to c^2 and to the heights,
+ * iou_loss.py:154-167, 230-231; ERD_BOX_GIOU: must be 1e-6, the value the kernel is built with).  Only the box term
+ * out[l][1] and its share of d/d bbox depend on the kind: the IoU score that feeds QFL stays bbox_overlaps' IoU
+ * (gfl_head_increment_erd.py:281-290), and so do weight_targets, the QFL / DFL sums and d/d cls.  ERD_BOX_GIOU is
+ * erd_gfl_losses_fwd / _bwd bit for bit.  Replaces self.loss_bbox(pos_decode_bbox_pred, pos_decode_bbox_targets, ...)
+ * at gfl_head_increment_erd.py:293-297 for IoULoss, DIoULoss and CIoULoss (iou_loss.py:307-389, 532-599, 603-670). */
+enum erd_box_loss {
+    ERD_BOX_GIOU = 0,
+    ERD_BOX_IOU_LOG = 1,     /* IoULoss(mode='log'):    -log(iou.clamp(min=eps)) */
+    ERD_BOX_IOU_LINEAR = 2,  /* IoULoss(mode='linear'): 1 - iou.clamp(min=eps) */
+    ERD_BOX_IOU_SQUARE = 3,  /* IoULoss(mode='square'): 1 - iou.clamp(min=eps)^2 */
+    ERD_BOX_DIOU = 4,
+    ERD_BOX_CIOU = 5
+};
+int erd_gfl_losses_fwd_box(const float* cls, const float* bbox, const float* anchors, const int64_t* labels,
+                           const float* label_weights, const float* bbox_targets, const int64_t* lvl_off,
+                           const int* strides, int nlvl, int N, int64_t A, int c_old, int c_all,
+                           float* score_ws, float* wt_ws, double* out_sums, int box_loss, float box_eps,
+                           erd_stream_t stream);
+int erd_gfl_losses_bwd_box(const float* cls, const float* bbox, const float* anchors, const int64_t* labels,
+                           const float* label_weights, const float* bbox_targets, const int64_t* lvl_off,
+                           const int* strides, int nlvl, int N, int64_t A, int c_old, int c_all,
+                           const float* score_ws, const float* wt_ws, const float* coef, float* dcls, float* dbbox,
+                           int box_loss, float box_eps, erd_stream_t stream);
 
 /* ---- response distillation (gfl_head_increment_erd.py:142-223) ------------------------------------ */
 /* L2 over ERS-selected rows: sums[n] = sum_{a in idx_cls[n], k<c_old} (s-t)^2 ; bwd adds coef[n]*2(s-t) */
@@ -647,6 +672,10 @@ int erd_coco_eval(const double* dt_box, const double* dt_score, const int32_t* d
  *   erd_dfl                      distribution_focal_loss over nb bins (gfocal_loss.py:143-165); rows and/or dpred
  *   erd_kd_kl_rows               knowledge_distillation_kl_div_loss, temperature T (kd_loss.py:12-37)
  *   erd_giou                     giou_loss rows 1 - GIoU and d/dpred (iou_loss.py:110-126; eps as bbox_overlaps clamps it)
+ *   erd_iou_loss                 iou_loss ('log' / 'linear' / 'square'), diou_loss, ciou_loss rows and d/dpred (iou_loss.py:16-54,
+ *                                130-181, 185-246): kind = enum erd_box_loss except ERD_BOX_GIOU (that is erd_giou), eps the
+ *                                module's `eps`.  Where the reference's fp32 value is not finite (ciou_loss on two identical
+ *                                boxes: alpha = 0 / 0) neither is the row
  *   erd_bbox_overlaps            bbox_overlaps mode 0 'iou' / 1 'giou', aligned [A] or pairwise [A][G] (bbox_overlaps.py:13-199)
  *   erd_integral                 Integral: softmax over nb bins . [0..nb-1] (gfl_head.py:29-62); y and/or dx
  *   erd_distance2bbox            DistancePointBBoxCoder.decode / distance2bbox (transforms.py:147-198), max_w < 0: no clamp;
@@ -669,6 +698,8 @@ int erd_kd_kl_rows(const float* pred, const float* soft, const float* coef, int6
                    erd_stream_t stream);
 int erd_giou(const float* pred, const float* target, const float* coef, int64_t n, float eps, float* rows, float* dpred,
              erd_stream_t stream);
+int erd_iou_loss(const float* pred, const float* target, const float* coef, int64_t n, int kind, float eps, float* rows,
+                 float* dpred, erd_stream_t stream);
 int erd_bbox_overlaps(const float* b1, const float* b2, int64_t A, int64_t G, int aligned, int mode, float eps, float* out,
                       erd_stream_t stream);
 int erd_integral(const float* x, const float* dy, int64_t m, int nb, float* y, float* dx, erd_stream_t stream);
